@@ -25,6 +25,11 @@ Other BASELINE.json configs as extra workloads (same JSON line, their own `confi
                    Adam(0.9, 0.99, 1e-15); 5120 rays per GPU -> 64 + 256 ray-samples per ray
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mip|n2v|barf|garf|ingp]
+                    [--full] [--dump-outputs DIR]
+    A plain run sets up, warms up, times the K steps and prints the line (the per-kernel figures in it
+    come from HIP events inside the timed steps).  --full adds the measurements that take runs of
+    their own: frame_render, roofline_hbm_frame and cpu_baseline.  --dump-outputs DIR writes what the
+    last timed step computed as DIR/<name>.npy.
     N>1: `python bench.py --gpus N` starts N rank processes itself (RANK / LOCAL_RANK / WORLD_SIZE,
     MASTER_ADDR 127.0.0.1, a free MASTER_PORT; launch_ranks), or run it under
     `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (WORLD_SIZE must equal N).
@@ -682,6 +687,29 @@ def run_timed(step, steps: int, warmup: int, dist, sync, device, on_timed_start=
     return elapsed, out
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all arrays together stay under 64 MB on disk
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """Write every tensor of `arrays` as <directory>/<name>.npy in float32 (float64 stays float64).
+    If together they exceed DUMP_BUDGET_BYTES, every array larger than its share is cut to a fixed
+    sample of its flattened elements (sorted indices from numpy's default_rng(0): the same elements
+    in every run and every build)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_BUDGET_BYTES // max(len(host), 1)
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def teardown(dist) -> None:
     if dist is not None:
         dist.destroy_process_group()
@@ -750,9 +778,20 @@ def main():
     ap.add_argument("--feed", default="device", choices=("device", "fixed"),
                     help="device: every step draws a fresh shuffled batch from 100 synthetic views through "
                          "the on-device ray feed (nerf_ray_batch); fixed: one resident batch reused")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements that take runs of their own: the "
+                         "full-frame render (frame_render), the full-frame launches of the PE / compositing "
+                         "kernels (roofline_hbm_frame) and the CPU oracle baseline (cpu_baseline); without it "
+                         "the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): train: loss, every parameter after the step (param.*) and its gradient "
+                         "(grad.*); render: rgb.  Same arguments, same inputs: two builds compare output for "
+                         "output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-frame-roofline", action="store_true",
-                    help="skip the full-frame launch measurement of the PE / compositing kernels")
+                    help="with --full: skip the full-frame render and the full-frame launch measurement of the "
+                         "PE / compositing kernels")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--matmul-precision", default="high", choices=("highest", "high", "medium"),
                     help="torch.set_float32_matmul_precision for the MLP GEMMs: highest = fp32 MFMA, "
@@ -793,11 +832,13 @@ def main():
     allreduce = BucketedGradAllReduce([p for m in modules for p in m.parameters()], direct=True)
     torch.manual_seed(1234 + rank)
     render = args.mode == "render"
+    last = {}                    # the last step's rendered rays (--dump-outputs)
 
     def step():
         if render:
             with torch.no_grad():
                 rgb, _ = render_fn()
+            last["rgb"] = rgb
             return rgb.mean()
         opt.zero_grad(set_to_none=True)
         loss = loss_fn()
@@ -812,6 +853,17 @@ def main():
     elapsed, loss = run_timed(step, args.steps, args.warmup, dist, torch.cuda.synchronize, device, start_timer)
     timer, K.TIMER = K.TIMER, None
     final_loss = float(loss.item())
+    if args.dump_outputs is not None and rank == 0:
+        if render:
+            arrays = {"rgb": last["rgb"]}
+        else:
+            arrays = {"loss": loss.reshape(1)}
+            for i, m in enumerate(modules):
+                for pname, p in m.named_parameters():
+                    arrays[f"param.{i}.{pname}"] = p
+                    if p.grad is not None:
+                        arrays[f"grad.{i}.{pname}"] = p.grad
+        dump_outputs(args.dump_outputs, arrays)
 
     samples_per_gpu = wl["rays"] * (wl["coarse"] + wl["fine"])
     samples_total = samples_per_gpu * world * args.steps
@@ -880,7 +932,7 @@ def main():
                                    / (elapsed / args.steps) / 1e12,
             ("mean_rgb" if render else "final_loss"): final_loss,
         }
-        if world == 1 and not args.no_frame_roofline:
+        if args.full and world == 1 and not args.no_frame_roofline:
             try:          # auxiliary measurements: their failure must not cost the bench line
                 out["frame_render"] = frame_render(ren, wl, device, args.workload)
             except Exception as e:      # noqa: BLE001
@@ -895,7 +947,7 @@ def main():
                 out["roofline_hbm_frame"] = fr
             except Exception as e:      # noqa: BLE001
                 out["roofline_hbm_frame"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline and not render:
+        if args.full and world == 1 and not args.no_cpu_baseline and not render:
             cb = cpu_baseline(args.workload, args.cpu_seconds)
             if cb is not None:
                 out["cpu_baseline"] = cb

@@ -96,3 +96,24 @@ def test_bench_self_launch_path_is_taken_before_any_gpu_call(tmp_path):
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["n"] == 2 and d["exit"] == 0 and d["cuda_init"] is False
     assert d["cmd"][1].endswith("bench.py") and d["cmd"][2:] == ["--gpus", "2", "--steps", "3"]
+
+
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample_over_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float32 (float64 kept); over the byte budget the
+    arrays larger than their share are cut to the same seeded sample of elements in every call."""
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(10000, dtype=torch.float32).reshape(100, 100)
+    arrays = {"loss": torch.tensor([0.25], dtype=torch.float64), "param.0.w": big, "half": torch.ones(3).half()}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert got["loss"].dtype == np.float64 and got["half"].dtype == np.float32
+    assert got["param.0.w"].dtype == np.float32 and np.array_equal(got["param.0.w"], big.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 4000)       # share: 4000 bytes = 1000 floats
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    b, c = np.load(tmp_path / "b" / "param.0.w.npy"), np.load(tmp_path / "c" / "param.0.w.npy")
+    assert b.shape == (1000,) and np.array_equal(b, c) and np.all(np.diff(b) >= 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "half.npy"), np.ones(3, np.float32))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 3 * 4000 + 3 * 128

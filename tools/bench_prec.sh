@@ -14,7 +14,7 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
   || { echo "gpu tests failed: $?"; tail -40 "$OUT/gpu_tests.txt"; exit 1; }
 tail -2 "$OUT/gpu_tests.txt"
 summ() { python3 -c "import json;d=json.load(open('$1'));print('$2', round(d['value']/1e6,2), 'M', round(d['ms_per_step'],3), 'ms', d['final_loss'], {k: round(v['ms_per_step'],3) for k, v in d['kernel_functions'].items()})"; }
-timeout -k 10 300 python -u bench.py --no-frame-roofline > "$OUT/bench_mip.json" 2> "$OUT/bench_mip.err" || { echo "bench mip failed"; tail -20 "$OUT/bench_mip.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-frame-roofline > "$OUT/bench_mip.json" 2> "$OUT/bench_mip.err" || { echo "bench mip failed"; tail -20 "$OUT/bench_mip.err"; exit 1; }
 summ "$OUT/bench_mip.json" mip
 for p in high medium; do
   timeout -k 10 300 python -u bench.py --workload n2v --matmul-precision $p --no-cpu-baseline --no-frame-roofline > "$OUT/bench_n2v_$p.json" 2> "$OUT/bench_n2v_$p.err" \

@@ -6,7 +6,7 @@ TAG=${1:-workloads}; shift || true
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for w in n2v mip barf; do
-  timeout -k 10 300 python -u bench.py --workload "$w" --no-cpu-baseline "$@" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" \
+  timeout -k 10 300 python -u bench.py --workload "$w" --full --no-cpu-baseline "$@" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" \
     || { echo "bench $w failed: $?"; tail -30 "$OUT/bench_$w.err"; exit 1; }
   cat "$OUT/bench_$w.json"
 done
