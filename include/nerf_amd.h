@@ -321,6 +321,33 @@ int nerf_linear_wgrad_x3_rays(const float* dY, int64_t ld_dy, const nerf_seg* se
                               int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
                               float* raysum, int32_t samples_per_ray0, int32_t samples_per_ray1,
                               int32_t passes, void* stream);
+/* Quad-split operand segments (added without an ABI bump: new entry points only, every existing
+ * signature and struct is unchanged and nerf_abi_version() stays 10).
+ *
+ * The quad-split image of an fp32 [M, ld] row-major matrix has the same shape, row stride and byte
+ * size.  The 16 bytes of each aligned group of 4 columns c .. c + 3 of a row hold
+ *   bytes 0-7:  hi[c], hi[c+1], hi[c+2], hi[c+3]   (bf16)
+ *   bytes 8-15: lo[c], lo[c+1], lo[c+2], lo[c+3]   (bf16)
+ * with hi = bf16(x), lo = bf16(x - float(hi)), both round-to-nearest-even: the two halves every
+ * split-precision kernel forms from x.  A producer that has them already stores them once, and
+ * the weight gradient copies the 16 bytes to its operand image instead of converting again.
+ *
+ * nerf_linear_wgrad_x3_rows_q / _rays_q are nerf_linear_wgrad_x3_rows / _rays with x_split_mask:
+ * bit j set = segment j of both blocks is a quad-split image (its nerf_seg.ptr / ld / k address it
+ * as the fp32 matrix it replaces; a view at a multiple of 32 columns stays a quad-split image).
+ * Bit-identical slabs to the same call on the fp32 values.  NERF_ERR_INVALID_ARG for a quad-split
+ * segment with row_div != 1, with N = 257 (the 257th row multiplies fp32 X), for a bit at or past
+ * n_segs, and for shapes that do not run the single 256 x 256 tile kernel (or with NERF_WGRAD_TR=0).
+ * The entry points without the mask pass 0. */
+int nerf_linear_wgrad_x3_rows_q(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
+                                const float* dY1, int64_t ld_dy1, const nerf_seg* segs1, int64_t M1,
+                                int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
+                                int32_t passes, uint32_t x_split_mask, void* stream);
+int nerf_linear_wgrad_x3_rays_q(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
+                                const float* dY1, int64_t ld_dy1, const nerf_seg* segs1, int64_t M1,
+                                int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
+                                float* raysum, int32_t samples_per_ray0, int32_t samples_per_ray1,
+                                int32_t passes, uint32_t x_split_mask, void* stream);
 int nerf_pack_weight_x3(const float* W, int32_t N, int32_t K_orig, const int32_t* col_map,
                         int32_t Kp, void* Wp_x, void* Wt_x, int32_t ldwt, void* stream);
 
@@ -467,6 +494,15 @@ int nerf_mlp_fused_render(const nerf_fused_layer* layers, int32_t n_layers, cons
  * reference's naive-to-vanilla/main.py:53,58 "medium" / 16-mixed C2 configuration) instead of the
  * 3 x bf16 split (hi*hi + hi*lo + lo*hi, ~2^-17 per product).  Same image, descriptors and outputs. */
 #define NERF_FUSED_BF16 1
+/* NERF_FUSED_SPLIT_OUT(l), bits 8 .. 8 + NERF_FUSED_MAX_LAYERS - 1 of flags (no ABI bump: a new
+ * flag on an existing argument, nerf_abi_version() stays 10): layer l of the split-precision forward
+ * stores its output as the QUAD-SPLIT image (see nerf_linear_wgrad_x3_rows_q) of the fp32 values it
+ * would have stored: same buffer, stride, bytes and stores, pad columns zero; the hi / lo halves are
+ * the ones the kernel forms for the next layer's operand, computed once.  ReLU mask bits, the column
+ * output and the heads still come from the fp32 values.  NERF_ERR_INVALID_ARG for the last layer, a
+ * layer with N > 256, with a column output or without an output buffer, with NERF_FUSED_BF16, and
+ * for the input-gradient chain. */
+#define NERF_FUSED_SPLIT_OUT(l) (1 << (8 + (l)))
 int nerf_mlp_fused_run(const nerf_fused_layer* layers, int32_t n_layers, const void* image, int64_t M,
                        const nerf_fused_encoding* encodings, const nerf_fused_composite* composite, int32_t flags,
                        void* stream);

@@ -762,6 +762,9 @@ struct TNArgs {
     // streamed kernel only: per-ray sums of dY (raysum[ray][n], rays of rs_S0 / rs_S1 samples in the
     // two blocks, block 1's rays after block 0's rs_B0) for a per-ray input's weight gradient, or null
     float* raysum; int rs_S0, rs_S1, rs_B0;
+    // transposed-read kernel only: bit j set = X segment j (of both blocks) is stored quad-split
+    // (nerf_amd.h: per 4 columns, 4 bf16 hi then 4 bf16 lo in the 16 bytes of the 4 fp32 values)
+    unsigned xsplit;
 };
 
 template <bool X1>
@@ -1276,6 +1279,16 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // Bias gradients, the 257th row (NerfModel's density + feature layer) and the per-ray dY sums of the
 // colour layer come from per-wave partials over the wave's rows, added in a fixed order (same values
 // as the stream kernel up to fp32 summation order).
+//
+// The loop exists once per role and kind of X (run below), chosen by wave-uniform branches before
+// it: the dY waves alone add the bias / per-ray partials, the X waves alone the 257th row, and a
+// wave whose 64 lanes read one operand with one source row per sample (every dY wave; X from a
+// single segment: the normal case) forms each row's base on the scalar ALU and adds its columns'
+// byte offset (wt_src_row_u) instead of selecting and multiplying per lane.  An X segment may be
+// stored quad-split (nerf_amd.h: the 16 bytes of 4 columns = their 4 bf16 hi halves, then their 4
+// lo halves, as a producer that split the values already stores them): the lane's 16 loaded bytes
+// are then the two ds_write_b64 payloads as they are, and no conversion runs (TNArgs::xsplit).
+// Same rows per wave in the same order, same products per accumulator: bit-identical outputs.
 constexpr int WT_T = 16;                          // samples per step
 constexpr int WT_IMG = 4 * WT_T * 512;            // image stage: [op][hi | lo][16 rows][256 cols] bf16
 constexpr int WT_RS = 4 * 256 * 4;                // per-ray partials of the 4 dY waves
@@ -1299,6 +1312,24 @@ __device__ __forceinline__ wt_gfp wt_src_row(wt_gfp s0, wt_gfp s1, int64_t ld0, 
     const unsigned rr = rd_one ? r : r / (b1 ? rd1 : rd0);
     return (b1 ? s1 : s0) + (int64_t)rr * (b1 ? ld1 : ld0);
 }
+// the same row when every lane of the wave reads one operand with one source row per sample: the
+// row's base from wave-uniform values (scalar ALU), the lane's columns as a byte offset added to it
+// (one v_lshl_add_u64 per load; the compiler keeps the zero-extended offset in a register pair
+// outside the loop, so the load is not selected in its scalar-base form)
+typedef const __attribute__((address_space(1))) char* wt_gcp;
+__device__ __forceinline__ wt_gcp wt_src_row_u(wt_gcp b0, wt_gcp b1, int64_t ldb0, int64_t ldb1, int M0, int mbeg,
+                                               int mend, int rel, unsigned voff) {
+    int m = mbeg + rel;
+    m = m < mend ? m : mbeg;
+    const bool b1f = m >= M0;
+    const unsigned r = (unsigned)(b1f ? m - M0 : m);
+    return (b1f ? b1 : b0) + (int64_t)r * (b1f ? ldb1 : ldb0) + voff;
+}
+// compile-time tags of the role-specialised loops
+template <int V>
+struct wt_tag {
+    static constexpr int value = V;
+};
 
 template <bool ROW257, bool RAYS, bool X1, int JN>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void linear_wgrad_x3_tr_kernel(
@@ -1328,6 +1359,9 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     gfp s0, s1;
     int64_t ld0, ld1;
     unsigned rd0 = 1, rd1 = 1, cmask = 0;
+    unsigned voff = 0;                        // byte offset of the lane's columns in its operand's rows
+    bool lane_u = true;                       // the lane reads segment 0 (or dY), one source row per sample
+    bool qs = false;                          // the lane's X segment is stored quad-split
     if (op == 0) {
         const int nval = N < 256 ? N : 256;
 #pragma unroll
@@ -1337,6 +1371,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         s1 = dY1 + col;
         ld0 = lddy0;
         ld1 = lddy1;
+        voff = 4u * (unsigned)col;
     } else {
         int xs = -1, xoff = 0;
 #pragma unroll
@@ -1355,7 +1390,18 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         s1 = (gfp)(ok ? pick4(a.x1ptr, xs) + xoff : a.x1ptr[0]);
         ld1 = ok ? pick4(a.x1ld, xs) : a.x1ld[0];
         rd1 = ok ? (unsigned)pick4(a.x1rd, xs) : (unsigned)a.x1rd[0];
+        voff = ok ? 4u * (unsigned)xoff : 0u;
+        lane_u = (!ok || xs == 0) && rd0 == 1u && rd1 == 1u;
+        qs = ok && ((a.xsplit >> xs) & 1u) != 0u;
     }
+    // The wave's loop (all four X-loading waves agree: each loads whole rows).  0: scalar row bases,
+    // fp32 rows (every dY wave; X from one segment, one source row per sample: the normal case);
+    // 1: the same with a quad-split X; 2: per-lane row addresses, fp32 and quad-split lanes mixed
+    const bool wave_u = __ballot(!lane_u) == 0;
+    const bool q_any = __ballot(qs) != 0;
+    const int xmode = !wave_u ? 2 : q_any ? 1 : 0;
+    const wt_gcp ub0 = (wt_gcp)(op == 0 ? a.dY : a.X.ptr[0]), ub1 = (wt_gcp)(op == 0 ? a.dY1 : a.x1ptr[0]);
+    const int64_t uld0 = 4 * (op == 0 ? lddy0 : a.X.ld[0]), uld1 = 4 * (op == 0 ? lddy1 : a.x1ld[0]);
     // one source row per sample in every lane of the wave (the row divisor is the per-ray input's,
     // absent from this kernel's layers in practice): no per-lane division
     const bool rd_one = __ballot(rd0 != 1u || rd1 != 1u) == 0;
@@ -1365,13 +1411,20 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #define WT_YD_ROW(i, q) wt_src_row(dY0 + 256, dY1 + 256, lddy0, lddy1, 1u, 1u, true, M0, mbeg, mend, (i) * WT_T + lr + (q))
     f4 ra[4], rb[4];                          // the two register stages: steps in flight
     float ya[4], yb[4];
-    auto issue = [&](int i, f4 (&r)[4], float (&y)[4]) __attribute__((always_inline)) {
+#define WT_SRC_ROW_U(i, q) wt_src_row_u(ub0, ub1, uld0, uld1, M0, mbeg, mend, (i) * WT_T + lr + (q), voff)
+    // (opc, modec: wt_tag<role>, wt_tag<loop>; the 257th row's dY column only in the X-loading waves)
+    auto issue = [&](auto opc, auto modec, int i, f4 (&r)[4], float (&y)[4]) __attribute__((always_inline)) {
 #ifdef NERF_WT_DIAG_NOLOAD     // diagnostic builds only: no row loads (converts the registers' stale values)
         if (i < 2)
 #endif
 #pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = __builtin_nontemporal_load((gf4p)WT_SRC_ROW(i, q));
-        if constexpr (ROW257) {
+        for (int q = 0; q < 4; ++q) {
+            if constexpr (decltype(modec)::value == 2)
+                r[q] = __builtin_nontemporal_load((gf4p)WT_SRC_ROW(i, q));
+            else
+                r[q] = __builtin_nontemporal_load((gf4p)WT_SRC_ROW_U(i, q));
+        }
+        if constexpr (ROW257 && decltype(opc)::value == 1) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) y[q] = *WT_YD_ROW(i, q);
         }
@@ -1391,30 +1444,35 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     for (int q = 0; q < 4; ++q) woff[q] = wt_off(op, 0, lr + q, 4 * lane);
 
     const bool cols_full = __ballot(cmask != 0xfu) == 0;   // wave-uniform: no padded column in the wave
-    auto convert = [&](int i, const f4 (&r)[4], const float (&y)[4]) __attribute__((always_inline)) {
+    // (role and loop as in issue: the bias / per-ray sums only in the dY-loading waves, the 257th
+    // row only in the X-loading waves, a quad-split row's 16 bytes written as they were loaded)
+    auto convert = [&](auto opc, auto modec, int i, const f4 (&r)[4], const float (&y)[4]) __attribute__((always_inline)) {
+        constexpr int OP = decltype(opc)::value, MODE = decltype(modec)::value;
         const int valid = mend - (mbeg + i * WT_T);          // rows of step i inside the split
         char* const img = smem + (i & 1) * WT_IMG;
-        f4 rv[4];
+        u32x4 rw[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) rv[q] = r[q];
+        for (int q = 0; q < 4; ++q) rw[q] = __builtin_bit_cast(u32x4, r[q]);
         if (!(cols_full && valid >= WT_T)) {                 // padded columns or the split's last rows
+            const bool q16 = MODE == 1 || (MODE == 2 && qs); // this lane's words hold two bf16 columns each
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const unsigned rm = lr + q < valid ? cmask : 0u;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    // through a scalar: __builtin_bit_cast of the vector element lvalue rv[q][e] reads
-                    // element 0 (hipcc), which filled the masked rows' columns 1-3 with column 0
-                    const float xe = rv[q][e];
-                    rv[q][e] = __builtin_bit_cast(float, __builtin_bit_cast(int, xe) &
-                                                             __builtin_amdgcn_sbfe((int)rm, (unsigned)e, 1u));
+                    // fp32: word e is column e; quad-split: word e holds columns 2 (e & 1), 2 (e & 1) + 1
+                    const unsigned m32 = (unsigned)__builtin_amdgcn_sbfe((int)rm, (unsigned)e, 1u);
+                    const unsigned m16 = ((unsigned)__builtin_amdgcn_sbfe((int)rm, 2u * (e & 1), 1u) & 0xffffu) |
+                                         ((unsigned)__builtin_amdgcn_sbfe((int)rm, 2u * (e & 1) + 1u, 1u) & 0xffff0000u);
+                    const unsigned we = rw[q][e];
+                    rw[q][e] = we & (MODE == 0 ? m32 : q16 ? m16 : m32);
                 }
             }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f4 v = rv[q];
-            if (op == 0) {
+            const f4 v = __builtin_bit_cast(f4, rw[q]);
+            if constexpr (OP == 0) {
                 dbp += v;
                 if constexpr (RAYS) rp += v;
             } else if constexpr (ROW257) {
@@ -1427,19 +1485,28 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             typedef float f2 __attribute__((ext_vector_type(2)));
             typedef unsigned u2 __attribute__((ext_vector_type(2)));
             u2 h, l;
+            if constexpr (MODE == 1) {
+                h = u2{rw[q][0], rw[q][1]};
+                l = u2{rw[q][2], rw[q][3]};
+            } else {
 #pragma unroll
-            for (int pp = 0; pp < 2; ++pp) {
-                const f2 x2 = {v[2 * pp], v[2 * pp + 1]};
-                const unsigned hp = __builtin_bit_cast(unsigned, __builtin_convertvector(x2, bf16x2));
-                const f2 hv = {__builtin_bit_cast(float, hp << 16), __builtin_bit_cast(float, hp & 0xffff0000u)};
-                h[pp] = hp;
-                l[pp] = __builtin_bit_cast(unsigned, __builtin_convertvector(x2 - hv, bf16x2));
+                for (int pp = 0; pp < 2; ++pp) {
+                    const f2 x2 = {v[2 * pp], v[2 * pp + 1]};
+                    const unsigned hp = __builtin_bit_cast(unsigned, __builtin_convertvector(x2, bf16x2));
+                    const f2 hv = {__builtin_bit_cast(float, hp << 16), __builtin_bit_cast(float, hp & 0xffff0000u)};
+                    h[pp] = hp;
+                    l[pp] = __builtin_bit_cast(unsigned, __builtin_convertvector(x2 - hv, bf16x2));
+                }
+                if constexpr (MODE == 2 && !ROW257) {
+                    h = qs ? u2{rw[q][0], rw[q][1]} : h;
+                    l = qs ? u2{rw[q][2], rw[q][3]} : l;
+                }
             }
             *reinterpret_cast<u2*>(img + woff[q]) = h;
             *reinterpret_cast<u2*>(img + woff[q] + WT_T * 512) = l;
         }
-        if constexpr (RAYS) {
-            if (op == 0 && valid > 0) {
+        if constexpr (RAYS && OP == 0) {
+            if (valid > 0) {
                 // rays end at step ends (16 | S; ray starts and splits at multiples of 128 rows)
                 const int last = mbeg + i * WT_T + (valid < WT_T ? valid : WT_T) - 1;
                 const bool b1 = last >= M0;
@@ -1522,30 +1589,28 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
             for (int j = 0; j < JN; ++j) acc[ii][j] = mfma_w<X1>(yh[ii], yl[ii], xh[j], xl[j], acc[ii][j]);
     };
-    // The two waves of a SIMD (wave w loads dY rows, wave w + 4 X rows) multiply at different times:
-    // the X-loading wave runs step i's MFMAs before converting step i + 1, its partner after, so one
-    // wave's conversion (VALU) runs under the other's MFMAs (profiles/r06k: the kernel 1.5-2 % faster
-    // in the mip step than both converting first; the roles swapped, or half of every wave's MFMAs
-    // before the conversion, no better).  Same products in the same order per accumulator.
-    auto mfma_pre = [&](int i) __attribute__((always_inline)) {
-        if (op == 1 && active) mfma_step(i);
-    };
-    auto mfma_post = [&](int i) __attribute__((always_inline)) {
-        if (op == 0 && active) mfma_step(i);
-    };
     auto barrier = []() __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's LDS writes / reads done
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    if (steps > 0) {
+    // One copy of the loop per role and kind of X (the choice is wave-uniform and fixed for the
+    // launch; every copy has the same barriers), so that no step carries the other role's sums as
+    // selects, or row addresses and conversions it does not need.
+    // The two waves of a SIMD (wave w loads dY rows, wave w + 4 X rows) multiply at different times:
+    // the X-loading wave runs step i's MFMAs before converting step i + 1, its partner after, so one
+    // wave's conversion (VALU) runs under the other's MFMAs (profiles/r06k: the kernel 1.5-2 % faster
+    // in the mip step than both converting first; the roles swapped, or half of every wave's MFMAs
+    // before the conversion, no better).  Same products in the same order per accumulator.
+    auto run = [&](auto opc, auto modec) __attribute__((always_inline)) {
+        constexpr int OP = decltype(opc)::value;
         // prologue: steps 0 and 1 in flight, step 0 converted, step 2 issued
-        issue(0, ra, ya);
-        issue(1, rb, yb);
-        convert(0, ra, ya);
-        issue(2, ra, ya);
-        if constexpr (RAYS) pend_ray = op == 0 ? ray_of_step(0) : -1;
+        issue(opc, modec, 0, ra, ya);
+        issue(opc, modec, 1, rb, yb);
+        convert(opc, modec, 0, ra, ya);
+        issue(opc, modec, 2, ra, ya);
+        if constexpr (RAYS && OP == 0) pend_ray = ray_of_step(0);
         barrier();
         // iteration i: convert step i + 1 (landed: issued two iterations ago), refill its registers
         // with step i + 3, multiply step i; unrolled by two so the register stages are compile-time
@@ -1553,28 +1618,47 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         // stage nobody reads, masked to zero: no branch around them, so the counted waits are exact)
         int i = 0;
         for (; i + 1 < steps; i += 2) {
-            mfma_pre(i);
-            convert(i + 1, rb, yb);
-            issue(i + 3, rb, yb);
-            flush_ray();
-            if constexpr (RAYS) pend_ray = op == 0 ? ray_of_step(i + 1) : -1;
-            mfma_post(i);
+            if (OP == 1 && active) mfma_step(i);
+            convert(opc, modec, i + 1, rb, yb);
+            issue(opc, modec, i + 3, rb, yb);
+            if constexpr (RAYS && OP == 0) {
+                flush_ray();
+                pend_ray = ray_of_step(i + 1);
+            }
+            if (OP == 0 && active) mfma_step(i);
             barrier();
-            mfma_pre(i + 1);
-            convert(i + 2, ra, ya);
-            issue(i + 4, ra, ya);
-            flush_ray();
-            if constexpr (RAYS) pend_ray = i + 2 < steps && op == 0 ? ray_of_step(i + 2) : -1;
-            mfma_post(i + 1);
+            if (OP == 1 && active) mfma_step(i + 1);
+            convert(opc, modec, i + 2, ra, ya);
+            issue(opc, modec, i + 4, ra, ya);
+            if constexpr (RAYS && OP == 0) {
+                flush_ray();
+                pend_ray = i + 2 < steps ? ray_of_step(i + 2) : -1;
+            }
+            if (OP == 0 && active) mfma_step(i + 1);
             barrier();
         }
         if (i < steps) {                       // odd step count: the last step, converted already
-            flush_ray();
-            if constexpr (RAYS) pend_ray = -1;
+            if constexpr (RAYS && OP == 0) {
+                flush_ray();
+                pend_ray = -1;
+            }
             if (active) mfma_step(i);
             barrier();
         }
-        flush_ray();
+        if constexpr (RAYS && OP == 0) flush_ray();
+    };
+    if (steps > 0) {
+        if (op == 0) {
+            run(wt_tag<0>{}, wt_tag<0>{});
+        } else if (xmode == 0) {
+            run(wt_tag<1>{}, wt_tag<0>{});
+        } else if (xmode == 1 && !ROW257) {
+            // (never with the 257th row: the entry point refuses the pair, and the kernel would fall
+            // through to the per-lane loop rather than leave its barriers)
+            if constexpr (!ROW257) run(wt_tag<1>{}, wt_tag<1>{});
+        } else {
+            run(wt_tag<1>{}, wt_tag<2>{});
+        }
     }
 
     float* slab = a.slab + (size_t)split * npad * kpad;
@@ -1969,7 +2053,8 @@ static const bool WGRAD_TR = [] {
 static int wgrad_x3_rows_impl(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
                               const float* dY1, int64_t ld_dy1, const nerf_seg* segs1, int64_t M1,
                               int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
-                              float* raysum, int32_t S0, int32_t S1, int32_t passes, void* stream) {
+                              float* raysum, int32_t S0, int32_t S1, int32_t passes, uint32_t x_split_mask,
+                              void* stream) {
     NERF_REQUIRE(passes == 1 || passes == 3);
     const bool x1 = passes == 1;
     // N need not be a multiple of 4: the kernels read dY in 4-column pieces up to pad4(N) <= ld_dy;
@@ -2026,6 +2111,18 @@ static int wgrad_x3_rows_impl(const float* dY, int64_t ld_dy, const nerf_seg* se
     } else {
         a.M0 = (int)M;
     }
+    // quad-split X segments: read by the transposed-read tile kernel alone, one source row per sample,
+    // and not beside the 257th row (whose products need the fp32 X)
+    NERF_REQUIRE((x_split_mask >> L.n) == 0);
+    if (x_split_mask != 0) {
+        // (the routes below, in their order: nerf_amd/kernels.py wgrad_reads_quad_split mirrors this)
+        const bool tile = !(N <= 16 && L.ktot <= 4 * SN_T && SMALLN_ON) && (N > 128 || L.ktot > 128) && N <= 256 &&
+                          L.ktot <= 256;
+        NERF_REQUIRE(tile && WGRAD_TR);
+        for (int i = 0; i < L.n; ++i)
+            if ((x_split_mask >> i) & 1u) NERF_REQUIRE(L.row_div[i] == 1 && a.x1rd[i] == 1);
+    }
+    a.xsplit = x_split_mask;
     // (M = 0 still launches: every split writes its zero slab, which the reduce reads)
     if (N <= 16 && L.ktot <= 4 * SN_T && SMALLN_ON) {                  // few output rows: vector-ALU stream
         const int n4 = (N + 3) / 4 * 4;
@@ -2083,12 +2180,30 @@ static int wgrad_x3_rows_impl(const float* dY, int64_t ld_dy, const nerf_seg* se
     return NERF_OK;
 }
 
+extern "C" int nerf_linear_wgrad_x3_rows_q(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
+                                           const float* dY1, int64_t ld_dy1, const nerf_seg* segs1, int64_t M1,
+                                           int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
+                                           int32_t passes, uint32_t x_split_mask, void* stream) {
+    return wgrad_x3_rows_impl(dY, ld_dy, segs, M0, dY1, ld_dy1, segs1, M1, n_segs, N, workspace, workspace_bytes,
+                              nullptr, 0, 0, passes, x_split_mask, stream);
+}
+
 extern "C" int nerf_linear_wgrad_x3_rows(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
                                          const float* dY1, int64_t ld_dy1, const nerf_seg* segs1, int64_t M1,
                                          int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
                                          int32_t passes, void* stream) {
+    return nerf_linear_wgrad_x3_rows_q(dY, ld_dy, segs, M0, dY1, ld_dy1, segs1, M1, n_segs, N, workspace,
+                                       workspace_bytes, passes, 0u, stream);
+}
+
+extern "C" int nerf_linear_wgrad_x3_rays_q(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
+                                           const float* dY1, int64_t ld_dy1, const nerf_seg* segs1, int64_t M1,
+                                           int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
+                                           float* raysum, int32_t samples_per_ray0, int32_t samples_per_ray1,
+                                           int32_t passes, uint32_t x_split_mask, void* stream) {
+    NERF_REQUIRE(raysum != nullptr);
     return wgrad_x3_rows_impl(dY, ld_dy, segs, M0, dY1, ld_dy1, segs1, M1, n_segs, N, workspace, workspace_bytes,
-                              nullptr, 0, 0, passes, stream);
+                              raysum, samples_per_ray0, samples_per_ray1, passes, x_split_mask, stream);
 }
 
 extern "C" int nerf_linear_wgrad_x3_rays(const float* dY, int64_t ld_dy, const nerf_seg* segs, int64_t M0,
@@ -2096,9 +2211,8 @@ extern "C" int nerf_linear_wgrad_x3_rays(const float* dY, int64_t ld_dy, const n
                                          int32_t n_segs, int32_t N, void* workspace, size_t workspace_bytes,
                                          float* raysum, int32_t samples_per_ray0, int32_t samples_per_ray1,
                                          int32_t passes, void* stream) {
-    NERF_REQUIRE(raysum != nullptr);
-    return wgrad_x3_rows_impl(dY, ld_dy, segs, M0, dY1, ld_dy1, segs1, M1, n_segs, N, workspace, workspace_bytes,
-                              raysum, samples_per_ray0, samples_per_ray1, passes, stream);
+    return nerf_linear_wgrad_x3_rays_q(dY, ld_dy, segs, M0, dY1, ld_dy1, segs1, M1, n_segs, N, workspace,
+                                       workspace_bytes, raysum, samples_per_ray0, samples_per_ray1, passes, 0u, stream);
 }
 
 extern "C" int nerf_linear_wgrad_x3(const float* dY, int64_t ld_dy, int32_t N, const nerf_seg* segs, int32_t n_segs,

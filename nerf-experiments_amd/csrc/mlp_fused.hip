@@ -80,6 +80,10 @@ constexpr int ST_AUX = 2;
 // of the 3 x bf16 split (lo * hi + hi * lo + hi * hi: "high")
 constexpr bool is_fwd(int mode) { return (mode & 1) == 0; }
 constexpr bool is_x1(int mode) { return (mode & 2) != 0; }
+// the split-precision forward with quad-split layer outputs (MODE_FWD | MODE_QS: a kernel of its
+// own, so that the plain forward carries none of it: with the switch read at run time in one
+// kernel the forward of the mip step ran 3.89 -> 4.05 ms, profiles/quad01)
+constexpr bool is_qs(int mode) { return (mode & 4) != 0; }
 template <int MODE>
 constexpr int after_dma_vm() { return is_fwd(MODE) ? 1 + 2 * SB : 2 * SB; }
 // Layer-output stores in chunk pairs: a 16-row chunk is 64 B of each sample row, half a 128-B line.
@@ -103,6 +107,7 @@ struct FusedArgs {
     int ntiles;
     int span;          // tiles a workgroup runs back to back (2: rays of 256 samples), ntiles % span == 0
     int comp_on;       // forward: composite every tile's rays (nerf_mlp_fused_render)
+    int split_mask;    // forward, split precision: bit l = layer l stores its output quad-split (nerf_amd.h)
     nerf_fused_composite comp;
     // a generated hash-grid encoding (params.kind 2): its parameters, table and level row offsets
     nerf_hashgrid_params hg;
@@ -216,6 +221,7 @@ __device__ __forceinline__ unsigned shift_in_dead(unsigned t, float x) {
 constexpr int MODE_FWD = 0;
 constexpr int MODE_DGRAD = 1;
 constexpr int MODE_X1 = 2;
+constexpr int MODE_QS = 4;
 
 struct Ctx {
     kchar_t* kargs;
@@ -559,6 +565,7 @@ __device__ __forceinline__ void comp_grad_block(const Ctx& c, int gen, const flo
 
 struct LayerState {
     int floor_i;          // ReLU as an integer max on the fp32 bits: 0, or INT_MIN for no ReLU
+    bool qsplit;          // forward: the output is stored quad-split (hi / lo words, formed once in part 0)
     int col_chunk;        // 16-row chunk holding the column output (-1: none)
     int n1;               // 16-row chunks routed to out (fed forward, masked); the rest go to out2
     unsigned bias_off;
@@ -661,13 +668,33 @@ __device__ __forceinline__ void epi_part(Ctx& c, LayerState& st, int p, int ch, 
             for (int r = 0; r < 4; ++r)
                 v[r] = __builtin_bit_cast(float, max(__builtin_bit_cast(int, v[r] + b[r]), st.floor_i));
             if (ch >= 0 && ch == st.col_chunk) c.sig[sb] = v[0];   // (the raw density, for fused compositing)
+            // what the stores below write: the fp32 values, or for a quad-split layer the hi / lo words
+            // u4{h01, h23, l01, l23} of the same 16 bytes — formed here once, for the store (and the
+            // stash) and for the next layer's operand image, which part 3 then leaves alone.  Same
+            // stores at the same addresses in the same order either way: the counted vmcnt waits hold
+            f4 sv = v;
+            if constexpr (is_qs(MODE)) {
+                if (st.qsplit) {
+                    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+                    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                    unsigned h0, l0, h1, l1;
+                    split2(v[0], v[1], h0, l0);
+                    split2(v[2], v[3], h1, l1);
+                    if (ch >= 0 && ch < 2 * KBMAX && ch < st.n1) {
+                        char* d = c.ximg + ((q * SB + sb) * 2) * 1024 + c.lane * 16 + 8 * bb;
+                        *reinterpret_cast<u2*>(d) = u2{h0, h1};
+                        *reinterpret_cast<u2*>(d + 1024) = u2{l0, l1};
+                    }
+                    sv = __builtin_bit_cast(f4, u4{h0, h1, l0, l1});
+                }
+            }
             if (EPAR >= 0 ? EPAR == 0 : !pair_odd(ch)) {
                 // even chunk: held for the pair (alone if it is the layer's last); the column output
                 // (col_idx is a multiple of 32: always an even chunk)
-                st.stash[sb] = v;
+                st.stash[sb] = sv;
                 const unsigned off =
                     ch >= 0 && ch == st.last_even && 16 * ch < st.colok ? st.row_off[sb] + 64u * (unsigned)ch : OOB;
-                __builtin_amdgcn_raw_buffer_store_b128(v, st.ro, off, 0, ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(sv, st.ro, off, 0, ST_AUX);
                 const unsigned coff = ch == st.col_chunk ? st.sample_off[sb] : OOB;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[0]), st.rc, coff, 0, 0);
             } else {
@@ -676,7 +703,7 @@ __device__ __forceinline__ void epi_part(Ctx& c, LayerState& st, int p, int ch, 
                 const unsigned oa = ch > 0 && 16 * (ch - 1) < st.colok ? st.row_off[sb] + 64u * (unsigned)(ch - 1) : OOB;
                 const unsigned ob = ch >= 0 && 16 * ch < st.colok ? st.row_off[sb] + 64u * (unsigned)ch : OOB;
                 __builtin_amdgcn_raw_buffer_store_b128(st.stash[sb], st.ro, oa, 0, ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(v, st.ro, ob, 0, ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(sv, st.ro, ob, 0, ST_AUX);
             }
         } else {
             const bool sec = ch >= st.n1;          // an encoding input's rows (out2): not masked
@@ -759,7 +786,7 @@ __device__ __forceinline__ void epi_part(Ctx& c, LayerState& st, int p, int ch, 
     } else {
         // rows 16 bb + 4 g + r of k-block q of the next layer = elements 4 bb + r of lane (s, g):
         // 8 bytes of the lane's 16-byte hi and lo slots (chunks past the fed outputs are not written)
-        if (ch >= 0 && ch < 2 * KBMAX && ch < st.n1) {
+        if (ch >= 0 && ch < 2 * KBMAX && ch < st.n1 && !(is_qs(MODE) && st.qsplit)) {
 #pragma unroll
             for (int sb = 0; sb < SB; ++sb) {
                 typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -867,6 +894,8 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
     LayerState st;
     const int ldo = (int)LF(int64_t, ldo, l);
     st.floor_i = LF(int, relu, l) != 0 ? 0 : (int)0x80000000;
+    st.qsplit = is_qs(MODE) &&
+                ((*(const __attribute__((address_space(4))) int*)(c.kargs + offsetof(FusedArgs, split_mask)) >> l) & 1) != 0;
     st.colok = ldo - 4 * g;
     st.last_even = (NC & 1) ? NC - 1 : -1;
     int sample[SB];
@@ -1508,7 +1537,8 @@ bool encoding_ok(const nerf_fused_encoding& e, int64_t M) {
 namespace {
 int fused_launch(const nerf_fused_layer* layers, int32_t n_layers, const void* image, int64_t M,
                  const nerf_fused_encoding* encodings, const nerf_fused_composite* comp, int32_t flags, void* stream) {
-    NERF_REQUIRE((flags & ~NERF_FUSED_BF16) == 0);
+    const int split_mask = (int)(((uint32_t)flags >> 8) & 0xffffu);
+    NERF_REQUIRE((flags & ~(NERF_FUSED_BF16 | (0xffff << 8))) == 0);
     const bool single_pass = (flags & NERF_FUSED_BF16) != 0;
     NERF_REQUIRE(layers != nullptr && image != nullptr);
     NERF_REQUIRE(n_layers >= 1 && n_layers <= NERF_FUSED_MAX_LAYERS);
@@ -1524,6 +1554,13 @@ int fused_launch(const nerf_fused_layer* layers, int32_t n_layers, const void* i
         if (dgrad)
             NERF_REQUIRE(layers[l].relu == 0 && layers[l].mask == nullptr && layers[l].col_out == nullptr);
     }
+    // quad-split layer outputs (NERF_FUSED_SPLIT_OUT): the split-precision forward only, layers that
+    // feed the next one from a buffer of <= 256 columns and have no column output
+    NERF_REQUIRE((split_mask >> n_layers) == 0 && (split_mask == 0 || (!dgrad && !single_pass)));
+    for (int l = 0; l < n_layers; ++l)
+        if ((split_mask >> l) & 1)
+            NERF_REQUIRE(l < n_layers - 1 && layers[l].N <= 256 && layers[l].col_out == nullptr &&
+                         layers[l].out != nullptr);
     for (int l = 0; l < n_layers; ++l) {
         const nerf_fused_layer& L = layers[l];
         const int kbr = (L.type / 3) * 4, kbh = L.type % 3;
@@ -1666,6 +1703,7 @@ int fused_launch(const nerf_fused_layer* layers, int32_t n_layers, const void* i
     a.span = 1;
     // compositing fused into the forward (include/nerf_amd.h nerf_fused_composite)
     a.comp_on = 0;
+    a.split_mask = split_mask;
     memset(&a.comp, 0, sizeof(a.comp));
     if (comp != nullptr) {
         a.comp = *comp;
@@ -1694,6 +1732,8 @@ int fused_launch(const nerf_fused_layer* layers, int32_t n_layers, const void* i
             hipLaunchKernelGGL(mlp_fused_kernel<MODE_FWD | MODE_X1>, dim3(grid), dim3(WG), 0, as_stream(stream), a);
     } else if (dgrad) {
         hipLaunchKernelGGL(mlp_fused_kernel<MODE_DGRAD>, dim3(grid), dim3(WG), 0, as_stream(stream), a);
+    } else if (split_mask != 0) {
+        hipLaunchKernelGGL(mlp_fused_kernel<MODE_FWD | MODE_QS>, dim3(grid), dim3(WG), 0, as_stream(stream), a);
     } else {
         hipLaunchKernelGGL(mlp_fused_kernel<MODE_FWD>, dim3(grid), dim3(WG), 0, as_stream(stream), a);
     }

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("NERF_AMD_LIB", os.path.join(_HERE, "libnerf_amd.so"))
 c_f = ctypes.c_float
 c_i32 = ctypes.c_int32
 c_i64 = ctypes.c_int64
+c_u32 = ctypes.c_uint32
 c_u64 = ctypes.c_uint64
 c_vp = ctypes.c_void_p
 c_sz = ctypes.c_size_t
@@ -36,6 +37,12 @@ NERF_EPI_TANH = 4096
 NERF_EPI_TANH_BWD = 8192
 NERF_ERR_UNSUPPORTED = -2
 NERF_FUSED_BF16 = 1
+
+
+def NERF_FUSED_SPLIT_OUT(layer: int) -> int:
+    """nerf_mlp_fused_run flag: layer `layer` stores its output quad-split (nerf_amd.h)."""
+    return 1 << (8 + layer)
+
 NERF_KABSCH_MAX_POINTS = 4096
 NERF_PROP_MAX_EDGES = 512
 NERF_GAUSS_FWD = 0
@@ -218,6 +225,12 @@ _SIGNATURES = {
     "nerf_linear_wgrad_x3_rays": (c_i32, [c_vp, c_i64, ctypes.POINTER(NerfSeg), c_i64, c_vp, c_i64,
                                           ctypes.POINTER(NerfSeg), c_i64, c_i32, c_i32, c_vp, c_sz, c_vp, c_i32,
                                           c_i32, c_i32, c_vp]),
+    "nerf_linear_wgrad_x3_rows_q": (c_i32, [c_vp, c_i64, ctypes.POINTER(NerfSeg), c_i64, c_vp, c_i64,
+                                            ctypes.POINTER(NerfSeg), c_i64, c_i32, c_i32, c_vp, c_sz, c_i32, c_u32,
+                                            c_vp]),
+    "nerf_linear_wgrad_x3_rays_q": (c_i32, [c_vp, c_i64, ctypes.POINTER(NerfSeg), c_i64, c_vp, c_i64,
+                                            ctypes.POINTER(NerfSeg), c_i64, c_i32, c_i32, c_vp, c_sz, c_vp, c_i32,
+                                            c_i32, c_i32, c_u32, c_vp]),
     "nerf_pack_weight_x3": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "nerf_mlp_fused_fwd": (c_i32, [ctypes.POINTER(NerfFusedLayer), c_i32, c_vp, c_i64,
                                    ctypes.POINTER(NerfFusedEncoding), c_vp]),

@@ -534,62 +534,114 @@ def linear_gauss_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch
     return True
 
 
+def quad_split_pack(x: torch.Tensor) -> torch.Tensor:
+    """The quad-split image of an fp32 [M, ld] tensor (ld % 4 == 0; nerf_amd.h): same shape, dtype
+    and bytes per row; the 16 bytes of columns c .. c + 3 (c % 4 == 0) hold hi[c .. c + 3] then
+    lo[c .. c + 3] as bf16, hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even."""
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] % 4:
+        raise ValueError("quad_split_pack: an fp32 [M, 4 n] tensor")
+    hi = x.bfloat16()
+    lo = (x - hi.float()).bfloat16()
+    q = torch.stack([hi.view(x.shape[0], -1, 4), lo.view(x.shape[0], -1, 4)], dim=2)   # [M, ld / 4, 2, 4] bf16
+    return q.contiguous().view(torch.float32).view(x.shape)
+
+
+def quad_split_unpack(q: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(hi, lo) as fp32 [M, ld] tensors from a quad-split image (quad_split_pack)."""
+    if q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] % 4:
+        raise ValueError("quad_split_unpack: an fp32-typed [M, 4 n] tensor")
+    h = q.contiguous().view(torch.bfloat16).view(q.shape[0], -1, 2, 4)
+    return h[:, :, 0].reshape(q.shape).float(), h[:, :, 1].reshape(q.shape).float()
+
+
 # the single-tile layers' weight-gradient kernel the library runs (NERF_WGRAD_TR=0: the LDS-DMA stream
 # kernel, default the register-staged transposed-read kernel; the same switch is read by the library),
 # for the timer's per-function grouping
-WGRAD_TILE_FN = ("linear_wgrad_x3_stream_kernel" if os.environ.get("NERF_WGRAD_TR", "1") == "0"
-                 else "linear_wgrad_x3_tr_kernel")
+WGRAD_TR = os.environ.get("NERF_WGRAD_TR", "1") != "0"
+WGRAD_SMALLN = os.environ.get("NERF_WGRAD_SMALLN", "1") != "0"
+WGRAD_TILE_FN = "linear_wgrad_x3_tr_kernel" if WGRAD_TR else "linear_wgrad_x3_stream_kernel"
 
 
-def linear_wgrad_x3(dY: torch.Tensor, N4: int, segs, M: int, workspace: torch.Tensor, passes: int = 3) -> None:
+def wgrad_single_tile(nrow: int, kpad: int) -> bool:
+    """Whether nerf_linear_wgrad_x3* runs a launch of nrow gradient rows (257, or the padded N) over
+    kpad packed input columns as ONE 256 x 256 tile per M split (the stream / transposed-read
+    kernel), as csrc/linear_x3.hip routes it: the timer's kernel names and the choice of quad-split
+    activations (mlp.split_layers) both ask here."""
+    if nrow <= 16 and kpad <= 2048 and WGRAD_SMALLN:
+        return False                                       # linear_wgrad_smalln_kernel
+    return (nrow > 128 or kpad > 128) and nrow <= 257 and kpad <= 256
+
+
+def wgrad_reads_quad_split(nrow: int, kpad: int) -> bool:
+    """Whether that launch may take quad-split X segments: the transposed-read tile kernel without
+    the 257th row (nerf_linear_wgrad_x3_rows_q's argument checks)."""
+    return WGRAD_TR and nrow <= 256 and wgrad_single_tile(nrow, kpad)
+
+
+def linear_wgrad_x3(dY: torch.Tensor, N4: int, segs, M: int, workspace: torch.Tensor, passes: int = 3,
+                    x_split_mask: int = 0) -> None:
     """Split-precision weight-gradient slabs (nerf_linear_wgrad_x3).  N4 is the row count: rounded
     up to 4 over a padded dY, or the true count (257: one 256 x 256 tile + a vector-ALU row); the
     workspace and the reduce take it rounded up to 4.  passes: 3 (3 x bf16 split) or 1 (one bf16
-    pass, matmul precision "medium")."""
+    pass, matmul precision "medium").  x_split_mask: bit j set = segment j is stored quad-split
+    (quad_split_pack; nerf_linear_wgrad_x3_rows_q, the single-tile kernel only)."""
     arr = make_segs(segs)
     kt = sum(k for _, k, _ in segs)
     # algorithmic bytes: dY and X read once, dW written once (the split-M slabs are the kernel's)
     # the C side runs one 256 x 256 tile per M split when the layer fits it (nerf_linear_wgrad_x3)
     kpad = sum(pad32(k) for _, k, _ in segs)
-    wide = (N4 > 128 or kpad > 128) and N4 <= 257 and kpad <= 256
+    wide = wgrad_single_tile(N4, kpad)
     end = TIMER.bracket("linear_wgrad_x3", 2.0 * M * N4 * kt, 4.0 * M * N4 + _segs_bytes(segs, M) + 4.0 * N4 * kt,
                         fn=WGRAD_TILE_FN if wide else
                         ("linear_wgrad_smalln_kernel" if N4 <= 16 else "linear_wgrad_x3_kernel")) \
         if TIMER is not None else None
-    st = _lib.load().nerf_linear_wgrad_x3(_ptr(dY), dY.stride(0), N4, arr, len(segs), M, _ptr(workspace),
-                                          workspace.numel() * workspace.element_size(), passes, _stream(dY.device))
+    if x_split_mask:
+        st = _lib.load().nerf_linear_wgrad_x3_rows_q(_ptr(dY), dY.stride(0), arr, M, None, 0, None, 0, len(segs), N4,
+                                                     _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                                     passes, x_split_mask, _stream(dY.device))
+    else:
+        st = _lib.load().nerf_linear_wgrad_x3(_ptr(dY), dY.stride(0), N4, arr, len(segs), M, _ptr(workspace),
+                                              workspace.numel() * workspace.element_size(), passes,
+                                              _stream(dY.device))
     if end is not None:
         end.record()
     _lib.check(st, "nerf_linear_wgrad_x3")
 
 
-def linear_wgrad_x3_rows(blocks, N4: int, workspace: torch.Tensor, passes: int = 3) -> None:
+def linear_wgrad_x3_rows(blocks, N4: int, workspace: torch.Tensor, passes: int = 3, x_split_mask: int = 0) -> None:
     """Split-precision weight-gradient slabs over two blocks of rows summed into one gradient
     (nerf_linear_wgrad_x3_rows): blocks = [(dY, segs, M), (dY1, segs1, M1)], the segments of the
-    same widths; the workspace and the reduce take M + M1."""
+    same widths; the workspace and the reduce take M + M1.  x_split_mask: bit j set = segment j of
+    both blocks is stored quad-split (nerf_linear_wgrad_x3_rows_q)."""
     (dY, segs, M), (dY1, segs1, M1) = blocks
     if any(k != k1 for (_, k, _), (_, k1, _) in zip(segs, segs1)) or len(segs) != len(segs1):
         raise ValueError("linear_wgrad_x3_rows: the blocks' segments differ in width")
     a0, a1 = make_segs(segs), make_segs(segs1)
     kt = sum(k for _, k, _ in segs)
     kpad = sum(pad32(k) for _, k, _ in segs)
-    wide = (N4 > 128 or kpad > 128) and N4 <= 257 and kpad <= 256
+    wide = wgrad_single_tile(N4, kpad)
     end = TIMER.bracket("linear_wgrad_x3", 2.0 * (M + M1) * N4 * kt,
                         4.0 * (M + M1) * N4 + _segs_bytes(segs, M) + _segs_bytes(segs1, M1) + 4.0 * N4 * kt,
                         fn=WGRAD_TILE_FN if wide else
                         ("linear_wgrad_smalln_kernel" if N4 <= 16 else "linear_wgrad_x3_kernel")) \
         if TIMER is not None else None
-    st = _lib.load().nerf_linear_wgrad_x3_rows(_ptr(dY), dY.stride(0), a0, M, _ptr(dY1), dY1.stride(0), a1, M1,
-                                               len(segs), N4, _ptr(workspace),
-                                               workspace.numel() * workspace.element_size(), passes,
-                                               _stream(dY.device))
+    if x_split_mask:
+        st = _lib.load().nerf_linear_wgrad_x3_rows_q(_ptr(dY), dY.stride(0), a0, M, _ptr(dY1), dY1.stride(0), a1, M1,
+                                                     len(segs), N4, _ptr(workspace),
+                                                     workspace.numel() * workspace.element_size(), passes,
+                                                     x_split_mask, _stream(dY.device))
+    else:
+        st = _lib.load().nerf_linear_wgrad_x3_rows(_ptr(dY), dY.stride(0), a0, M, _ptr(dY1), dY1.stride(0), a1, M1,
+                                                   len(segs), N4, _ptr(workspace),
+                                                   workspace.numel() * workspace.element_size(), passes,
+                                                   _stream(dY.device))
     if end is not None:
         end.record()
     _lib.check(st, "nerf_linear_wgrad_x3_rows")
 
 
 def linear_wgrad_x3_rays(blocks, N4: int, workspace: torch.Tensor, raysum: torch.Tensor, S0: int, S1: int,
-                        passes: int = 3) -> None:
+                        passes: int = 3, x_split_mask: int = 0) -> None:
     """linear_wgrad_x3_rows (streamed single-tile kernel) that also writes the per-ray sums of dY into
     raysum [B0 + B1, N4] (nerf_linear_wgrad_x3_rays); blocks as linear_wgrad_x3_rows, M1 may be 0."""
     (dY, segs, M), (dY1, segs1, M1) = blocks
@@ -601,10 +653,16 @@ def linear_wgrad_x3_rays(blocks, N4: int, workspace: torch.Tensor, raysum: torch
                         4.0 * (M + M1) * N4 + _segs_bytes(segs, M) + _segs_bytes(segs1, M1) + 4.0 * N4 * kt
                         + 4.0 * raysum.numel(), fn=WGRAD_TILE_FN) \
         if TIMER is not None else None
-    st = _lib.load().nerf_linear_wgrad_x3_rays(_ptr(dY), dY.stride(0), a0, M, _ptr(dY1), dY1.stride(0), a1, M1,
-                                               len(segs), N4, _ptr(workspace),
-                                               workspace.numel() * workspace.element_size(), _ptr(raysum), S0, S1,
-                                               passes, _stream(dY.device))
+    if x_split_mask:
+        st = _lib.load().nerf_linear_wgrad_x3_rays_q(_ptr(dY), dY.stride(0), a0, M, _ptr(dY1), dY1.stride(0), a1, M1,
+                                                     len(segs), N4, _ptr(workspace),
+                                                     workspace.numel() * workspace.element_size(), _ptr(raysum), S0,
+                                                     S1, passes, x_split_mask, _stream(dY.device))
+    else:
+        st = _lib.load().nerf_linear_wgrad_x3_rays(_ptr(dY), dY.stride(0), a0, M, _ptr(dY1), dY1.stride(0), a1, M1,
+                                                   len(segs), N4, _ptr(workspace),
+                                                   workspace.numel() * workspace.element_size(), _ptr(raysum), S0,
+                                                   S1, passes, _stream(dY.device))
     if end is not None:
         end.record()
     _lib.check(st, "nerf_linear_wgrad_x3_rays")

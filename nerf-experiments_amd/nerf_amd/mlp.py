@@ -159,7 +159,7 @@ def _ray_split(blocks, N4: int):
     return mains, rays
 
 
-def _wgrad_rays(blocks, N4: int, lp, workspace, gW, gb, acc, split, npass: int = 3) -> None:
+def _wgrad_rays(blocks, N4: int, lp, workspace, gW, gb, acc, split, npass: int = 3, q=()) -> None:
     """The weight gradient of `blocks` (one or two passes' rows) through the per-ray route (_ray_split)."""
     mains, rays = split
     Mt = sum(M for _, _, M in blocks)
@@ -170,7 +170,8 @@ def _wgrad_rays(blocks, N4: int, lp, workspace, gW, gb, acc, split, npass: int =
     b0 = (blocks[0][0], mains[0], blocks[0][2])
     b1 = (blocks[1][0], mains[1], blocks[1][2]) if len(blocks) > 1 else (blocks[0][0], mains[0], 0)
     ws = _wgrad_workspace(workspace, Mt, N4, kmain)
-    K.linear_wgrad_x3_rays([b0, b1], N4, ws, raysum, rays[0][2], rays[1][2] if len(blocks) > 1 else 0, passes=npass)
+    K.linear_wgrad_x3_rays([b0, b1], N4, ws, raysum, rays[0][2], rays[1][2] if len(blocks) > 1 else 0, passes=npass,
+                           x_split_mask=_qmask(q, range(len(mains[0]))))
     K.linear_wgrad_reduce(Mt, N4, kmain, lp.N, ws, lp.col_map[:kmain], gW, gb, accumulate=acc)
     kray = K.pad32(rays[0][1])
     Bt = sum(Bs)
@@ -228,7 +229,7 @@ def _tile_split(segs, nrow: int):
     return rows, groups
 
 
-def _wgrad_tiles(blocks, nrow: int, N4: int, lp, workspace, gW, gb, acc, split, npass: int) -> None:
+def _wgrad_tiles(blocks, nrow: int, N4: int, lp, workspace, gW, gb, acc, split, npass: int, q=()) -> None:
     """The weight gradient of `blocks` (one or two passes' rows) tile by tile (_tile_split)."""
     rows, groups = split
     Mt = sum(M for _, _, M in blocks)
@@ -251,31 +252,123 @@ def _wgrad_tiles(blocks, nrow: int, N4: int, lp, workspace, gW, gb, acc, split, 
             p0 = poff[g[0][0]] + g[0][1]
             kp = sum(K.pad32(c1 - c0) for _, c0, c1 in g)
             ws = _wgrad_workspace(workspace, Mt, n4, kp)
+            qm = _qmask(q, [j for j, _, _ in g])
             if len(pb) > 1:
-                K.linear_wgrad_x3_rows(pb, nr, ws, passes=npass)
+                K.linear_wgrad_x3_rows(pb, nr, ws, passes=npass, x_split_mask=qm)
             else:
-                K.linear_wgrad_x3(pb[0][0], nr, pb[0][1], pb[0][2], ws, passes=npass)
+                K.linear_wgrad_x3(pb[0][0], nr, pb[0][1], pb[0][2], ws, passes=npass, x_split_mask=qm)
             K.linear_wgrad_reduce(Mt, n4, kp, nvalid, ws, lp.col_map[p0:p0 + kp], gW[n0:n0 + nvalid],
                                   gb[n0:n0 + nvalid] if gi == 0 else None, accumulate=acc)
+
+
+def _qmask(q, js) -> int:
+    """x_split_mask of a launch whose segment i is the layer's segment js[i] (q: per segment of the
+    layer, whether it is stored quad-split)."""
+    return sum(1 << i for i, j in enumerate(js) if j < len(q) and q[j])
+
+
+def _wgrad_x3(blocks, nrow: int, N4: int, lp, workspace, gW, gb, acc, npass: int, q=()) -> None:
+    """The split-precision weight gradient of `blocks` (one or two passes' rows) by the route
+    wgrad_launches describes: per-ray sums, single-tile launches, or one launch."""
+    segs = blocks[0][1]
+    rsplit = _ray_split(blocks, N4) if nrow == N4 else None
+    tsplit = _tile_split(segs, nrow) if rsplit is None else None
+    if rsplit is not None:
+        _wgrad_rays(blocks, N4, lp, workspace, gW, gb, acc, rsplit, npass, q)
+    elif tsplit is not None:
+        _wgrad_tiles(blocks, nrow, N4, lp, workspace, gW, gb, acc, tsplit, npass, q)
+    else:
+        Mt = sum(M for _, _, M in blocks)
+        qm = _qmask(q, range(len(segs)))
+        ws = _wgrad_workspace(workspace, Mt, N4, lp.Kp)
+        if len(blocks) > 1:
+            K.linear_wgrad_x3_rows(blocks, nrow, ws, passes=npass, x_split_mask=qm)
+        else:
+            K.linear_wgrad_x3(blocks[0][0], nrow, segs, blocks[0][2], ws, passes=npass, x_split_mask=qm)
+        K.linear_wgrad_reduce(Mt, N4, lp.Kp, lp.N, ws, lp.col_map, gW, gb, accumulate=acc)
+
+
+def wgrad_launches(segs, nrow: int, N4: int, M: int, rays: bool = True):
+    """The launches _wgrad_x3 makes for a layer with segments (tensor or None, k, row divisor), as
+    [(gradient rows, [(segment, packed columns)])]: decided by the same _ray_split / _tile_split."""
+    rsplit = _ray_split([(None, segs, M)], N4) if rays and nrow == N4 else None
+    if rsplit is not None:
+        n = len(segs) - 1
+        return [(N4, [(j, K.pad32(segs[j][1])) for j in range(n)]), (N4, [(n, K.pad32(segs[n][1]))])]
+    tsplit = _tile_split(segs, nrow)
+    if tsplit is not None:
+        rows, groups = tsplit
+        return [(nrow if len(rows) == 1 else nb, [(j, K.pad32(c1 - c0)) for j, c0, c1 in g])
+                for _, nb in rows for g in groups]
+    return [(nrow, [(j, K.pad32(k)) for j, (_, k, _) in enumerate(segs)])]
+
+
+# The fused forward stores a hidden activation QUAD-SPLIT (include/nerf_amd.h: the bf16 hi / lo halves
+# it forms anyway for the next layer's operand, in the 16 bytes of the 4 fp32 values) when the only
+# later reader is the weight-gradient tile kernel, which then copies the halves instead of splitting
+# the values again.  False: fp32 activations everywhere.  Off by default: measured on the mip step the
+# forward kernel that writes the format costs more than the weight gradients gain (DESIGN.md §3,
+# profiles/quad01/ab_save_split.txt)
+SAVE_SPLIT = False
+
+
+def split_layers(plan, M: int, dir_rd: int) -> frozenset:
+    """The layers whose stored output the fused split-precision forward (with autograd) writes
+    quad-split: fed to the next layer's registers only, never exposed, and read by the backward
+    only through weight-gradient launches that take the format (K.wgrad_reads_quad_split)."""
+    if not SAVE_SPLIT or CAPTURE is not None or not mlp_fused.dgrad_eligible(plan, M):
+        return frozenset()
+    cols = {li for li, _ in plan.column_outputs}
+    out = set()
+    for l, lp in enumerate(plan.layers[:-1]):
+        if lp.N > 256 or l in plan.outputs or l in cols or lp.gauss is not None or lp.tanh:
+            continue
+        readers = [(c, si) for c, cl in enumerate(plan.layers) for si, s in enumerate(cl.sources)
+                   if s.kind == "act" and s.layer == l]
+        if not readers or any(cl.residual == l for cl in plan.layers):
+            continue
+        ok = True
+        for c, si in readers:
+            cl = plan.layers[c]
+            if c != l + 1 or si != 0 or cl.N == 257:        # the register-fed operand; no 257th row
+                ok = False
+                break
+            N4 = (cl.N + 3) // 4 * 4
+            segs = [(None, s.k_seg, dir_rd if s.kind == "dir" else 1) for s in cl.sources]
+            for rays in (True, False):                      # (a merged second pass may drop the per-ray route)
+                for nr, piece in wgrad_launches(segs, N4, N4, M, rays):
+                    if any(j == si for j, _ in piece) and not K.wgrad_reads_quad_split(nr, sum(kp for _, kp in piece)):
+                        ok = False
+        if ok:
+            out.add(l)
+    return frozenset(out)
+
+
+def fused_mask_to_maskout(mask: torch.Tensor) -> torch.Tensor:
+    """ReLU bits of the fused forward (NERF_FUSED_MASK: set = dead, per MFMA lane) as the
+    NERF_EPI_MASKOUT bits the layer-by-layer input-gradient GEMMs read (set = out > 0)."""
+    M = mask.shape[0]
+    w = mask.view(torch.int32).view(M, 8)
+    n = torch.arange(256, device=mask.device)
+    c, g, r = n // 16, (n // 4) % 4, n % 4
+    alive = ((w[:, 2 * g + (c // 8)] >> (4 * (7 - (c % 8)) + r)) & 1) == 0          # [M, 256]
+    # column 4 (32 h + b) + e is bit b of word 2 e + h
+    bits = alive.view(M, 2, 32, 4).permute(0, 3, 1, 2).to(torch.int64)              # [M, e, h, b]
+    words = (bits << torch.arange(32, device=mask.device)).sum(-1)                  # [M, e, h]
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+    return words.reshape(M, 8).contiguous().view(torch.uint8).view(M, 32)
 
 
 def _flush_wgrad(entry, sink) -> None:
     """A stashed pass whose partner never ran its backward (BucketedGradAllReduce.finish()): its
     weight gradient alone, landed as the sink expects."""
-    dZ, segs, M, nrow, N4, lp, npass = entry
+    dZ, segs, M, nrow, N4, lp, npass, q = entry
     w, b = lp.module.weight, lp.module.bias
     gW, acc = sink.target(w)
     gb, _ = sink.target(b)
     ws = torch.empty((K.linear_wgrad_workspace_bytes(M, N4, lp.Kp) + 3) // 4, device=dZ.device, dtype=torch.float32)
-    rsplit = _ray_split([(dZ, segs, M)], N4) if nrow == N4 else None
-    tsplit = _tile_split(segs, nrow) if rsplit is None else None
-    if rsplit is not None:          # the route the unmerged backward takes: the same result, bitwise
-        _wgrad_rays([(dZ, segs, M)], N4, lp, ws, gW, gb, acc, rsplit, npass)
-    elif tsplit is not None:
-        _wgrad_tiles([(dZ, segs, M)], nrow, N4, lp, ws, gW, gb, acc, tsplit, npass)
-    else:
-        K.linear_wgrad_x3(dZ, nrow, segs, M, ws, passes=npass)
-        K.linear_wgrad_reduce(M, N4, lp.Kp, lp.N, ws, lp.col_map, gW, gb, accumulate=acc)
+    # the route the unmerged backward takes: the same result, bitwise
+    _wgrad_x3([(dZ, segs, M)], nrow, N4, lp, ws, gW, gb, acc, npass, q)
     sink.landed(w)
     sink.landed(b)
 
@@ -487,6 +580,7 @@ class MLPFunction(torch.autograd.Function):
         # (NerfModel with delayed density never reads z_last: a 268 MB memset + clone per step)
         ctx.set_materialize_grads(False)
         ctx.fused_forward = False
+        ctx.split = frozenset()
         comp = getattr(plan, "composite", None)
         plan.composite = None
         ctx.comp = None
@@ -514,6 +608,8 @@ class MLPFunction(torch.autograd.Function):
                 masks.append(torch.empty(M, 32, device=pos.device, dtype=torch.uint8)
                              if keep_all and lp.relu and plan.consumed[idx] and lp.N <= 256 else None)
             col_t = {li: torch.empty(M, device=pos.device, dtype=torch.float32) for li, _ in plan.column_outputs}
+            # hidden activations only the weight gradients read again: stored as the hi / lo halves
+            split = split_layers(plan, M, dir_rd) if keep_all and passes(prec) == 3 else frozenset()
             # deferred encodings (render_raw) are generated by the kernel itself, their rows stored by
             # the first layer that reads them
             if comp is not None:
@@ -524,7 +620,8 @@ class MLPFunction(torch.autograd.Function):
                              if keep_all else None)
             fused.run(M, pos, dirs, dir_rd, acts, masks, col_t, (K.deferred(pos), K.deferred(dirs)),
                       comp=(comp, rgb, w, composite_sigma_layer(plan)) if comp is not None else None,
-                      passes=passes(prec))
+                      passes=passes(prec), split_out=sorted(split))
+            ctx.split = split
             K.mark_filled(pos)
             K.mark_filled(dirs)
             cols = tuple(col_t[li] for li, _ in plan.column_outputs)
@@ -759,13 +856,15 @@ class MLPFunction(torch.autograd.Function):
             N4 = (lp.N + 3) // 4 * 4
             # the true row count: 257 (density + features) runs as one 256 x 256 tile + a row
             nrow = lp.N if (lp.N == 257 and WGRAD_ROW257) else N4
+            # which segments are quad-split images (ctx.split: chosen by the forward)
+            q = tuple(s.kind == "act" and s.layer in ctx.split for s in lp.sources)
             merge = sink is not None and is_split(ctx.prec) and MERGE_PASSES and gs is None
             prev = sink.stash.pop((id(plan), li), (None, None))[0] if merge else None
             if merge and prev is None and sink.remaining(w) >= 2:
                 # another pass of this field lands its contribution later in this backward: its
                 # weight gradient runs once over both passes' rows (one launch, one reduce); the
                 # sink flushes the stash alone if that pass never comes
-                sink.stash[(id(plan), li)] = ((dZ, segs, M, nrow, N4, lp, passes(ctx.prec)), _flush_wgrad)
+                sink.stash[(id(plan), li)] = ((dZ, segs, M, nrow, N4, lp, passes(ctx.prec), q), _flush_wgrad)
                 layer_grads[li] = [None, None]
             else:
                 if sink is not None:
@@ -775,24 +874,15 @@ class MLPFunction(torch.autograd.Function):
                         raise RuntimeError("direct gradient sink: weight and bias of one layer out of step")
                 else:
                     gW, gb, acc = torch.empty_like(w), torch.empty_like(lp.module.bias), False
-                rsplit = None
-                wblocks = [(prev[0], prev[1], prev[2]), (dZ, segs, M)] if prev is not None else [(dZ, segs, M)]
-                if is_split(ctx.prec) and nrow == N4:
-                    rsplit = _ray_split(wblocks, N4)
                 npass = passes(ctx.prec)
-                tsplit = _tile_split(segs, nrow) if rsplit is None and is_split(ctx.prec) else None
-                if rsplit is not None:
-                    _wgrad_rays(wblocks, N4, lp, workspace, gW, gb, acc, rsplit, npass)
-                elif tsplit is not None:
-                    _wgrad_tiles(wblocks, nrow, N4, lp, workspace, gW, gb, acc, tsplit, npass)
-                elif prev is not None:
-                    pdZ, psegs, pM = prev[0], prev[1], prev[2]
-                    ws = _wgrad_workspace(workspace, M + pM, N4, lp.Kp)
-                    K.linear_wgrad_x3_rows([(pdZ, psegs, pM), (dZ, segs, M)], nrow, ws, passes=npass)
-                    K.linear_wgrad_reduce(M + pM, N4, lp.Kp, lp.N, ws, lp.col_map, gW, gb, accumulate=acc)
+                if prev is not None and prev[7] != q:
+                    # the two passes stored this input in different formats (one of them could not
+                    # take the chain): one launch each, the second accumulating
+                    _wgrad_x3([(prev[0], prev[1], prev[2])], nrow, N4, lp, workspace, gW, gb, acc, npass, prev[7])
+                    _wgrad_x3([(dZ, segs, M)], nrow, N4, lp, workspace, gW, gb, True, npass, q)
                 elif is_split(ctx.prec):
-                    K.linear_wgrad_x3(dZ, nrow, segs, M, workspace, passes=npass)
-                    K.linear_wgrad_reduce(M, N4, lp.Kp, lp.N, workspace, lp.col_map, gW, gb, accumulate=acc)
+                    wblocks = [(prev[0], prev[1], prev[2]), (dZ, segs, M)] if prev is not None else [(dZ, segs, M)]
+                    _wgrad_x3(wblocks, nrow, N4, lp, workspace, gW, gb, acc, npass, q)
                 else:
                     K.linear_wgrad(dZ, N4, segs, M, workspace)
                     K.linear_wgrad_reduce(M, N4, lp.Kp, lp.N, workspace, lp.col_map, gW, gb, accumulate=acc)
@@ -832,6 +922,11 @@ class MLPFunction(torch.autograd.Function):
                         if ctx.masks[j] is not None and not ctx.fused_forward:
                             epi |= NERF_EPI_MASK | NERF_EPI_MASKBITS
                             aux = ctx.masks[j]
+                        elif j in ctx.split:
+                            # a quad-split activation is not a value to compare with 0: the fused
+                            # forward's bits, converted to the layout this kernel reads
+                            epi |= NERF_EPI_MASK | NERF_EPI_MASKBITS
+                            aux = fused_mask_to_maskout(ctx.masks[j])
                         else:
                             epi |= NERF_EPI_MASK
                             aux = acts[j]

@@ -214,14 +214,15 @@ class FusedForward:
         _pack_image(self)
 
     def run(self, M: int, pos: torch.Tensor, dirs: torch.Tensor | None, dir_rd: int, acts, masks, col_outs,
-            gens=(None, None), comp=None, passes: int = 3):
+            gens=(None, None), comp=None, passes: int = 3, split_out=()):
         """Launch on the current stream.  acts[l]: [M, out_ld] fp32 or None (not stored),
         masks[l]: [M, 32] uint8 or None, col_outs: {layer: [M] fp32}.  gens: the DeferredEncoding
         of pos / dirs or None: generated in-kernel at every tile start (kernels.encode_fwd(defer=True))
         and stored into the tensor, which later layers read; the first layer reads them from LDS.
         comp: (CompositeSpec, rgb [B, 3], weights [B, S], sigma layer) — the rays composited at the
         end of every tile (nerf_mlp_fused_render), coefficients into spec.coef when it is set.
-        passes: 3 (3 x bf16 split products) or 1 (one bf16 pass: matmul precision "medium")."""
+        passes: 3 (3 x bf16 split products) or 1 (one bf16 pass: matmul precision "medium").
+        split_out: layers whose output is stored quad-split (NERF_FUSED_SPLIT_OUT; mlp.split_layers)."""
         self.pack()
         L = len(self.plan.layers)
         descs = (_lib.NerfFusedLayer * L)()
@@ -317,13 +318,16 @@ class FusedForward:
             nbytes += 4.0 * M + 12.0 * (M // spec.S) + (4.0 * M if w is not None else 0.0) \
                 + (32.0 * M if spec.coef is not None else 0.0)
         end = K.TIMER.bracket("mlp_fused_fwd", flops, nbytes + self.image.numel() * self.image.element_size(),
-                              fn="mlp_fused_kernel<0>" if passes == 3 else "mlp_fused_kernel<2>") \
+                              fn=("mlp_fused_kernel<4>" if split_out else "mlp_fused_kernel<0>") if passes == 3
+                              else "mlp_fused_kernel<2>") \
             if K.TIMER is not None else None
         st = _lib.load().nerf_mlp_fused_run(descs, L, self.image.data_ptr(), M, encs if gen_of else None,
                                             ctypes.byref(cdesc) if cdesc is not None else None,
-                                            _flags(passes), K._stream(self.device))
+                                            _flags(passes) | sum(_lib.NERF_FUSED_SPLIT_OUT(l) for l in split_out),
+                                            K._stream(self.device))
         if end is not None:
             end.record()
+        self.last_flags = _flags(passes) | sum(_lib.NERF_FUSED_SPLIT_OUT(l) for l in split_out)
         _lib.check(st, "nerf_mlp_fused_fwd")
 
 
