@@ -554,6 +554,59 @@ int nerf_gauss_act_bwd(const float* grad_y, int64_t ld_g, const float* z, int64_
                        void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Gabor and Sarf activations with learnable per-channel parameters (GaborF / SARF field MLPs,
+ * the two other members of GARF's family; new entry points only, nerf_abi_version() stays 10).
+ * kind NERF_ACT_GABOR (gaborf/gabor.py:8-64): p0 = inv_standard_deviation s, p1 = spread p,
+ *   v_n = s_n^2 + 1e-6;  y = exp((-(z*z)) * v) * cos(p*z).
+ *   Backward (the reference's hand-written one): go = (-exp((-(z*z)) * v)) * grad_y;
+ *   grad_z = go * (((2*cos(pz)) * v) * z + p * sin(pz));
+ *   grad_p0_n = (sum_m (go * z^2) * cos(pz)) * (2 * s_n);  grad_p1_n = sum_m (go * z) * sin(pz).
+ * kind NERF_ACT_SARF (sarf/activation.py:40-65, the cos * exp form SarfAct.forward returns):
+ *   p0 = frequency f, p1 = NULL (grad_p1 = NULL);  t = |z| + 1e-4, u = t^2, q = u + 1/(f*f),
+ *   a = f/q;  y = cos(a) * exp(-u).
+ *   Backward: grad_z = grad_y * (exp(-u) * ((sin(a)*f)/(q*q) - cos(a))) * (2 * t * sign(z)) with
+ *   sign(+-0) = 0 (grad_z is exactly 0 there);
+ *   grad_p0_n = sum_m grad_y * ((-sin(a)) * exp(-u)) * (1/q + 2/((f*f)*(q*q))).
+ *   f == 0 is outside the contract (the reference's own gradient is not finite there).
+ * The sin / cos argument keeps its rounding error (p*z as the exact product hi + lo; f/q formed in
+ * fp64 and split), since one fp32 ulp of it would enter y undamped; all else is fp32 arithmetic.
+ * Kind 0 is reserved and refused.  z, y, grad_y, grad_z are [M][N] row-major with their own row
+ * strides (>= N); grad_z may alias grad_y.  The column sums are accumulated in fp64 per slab of
+ * rows (one partial row per slab and parameter) and the slabs summed in a fixed order
+ * (deterministic, no atomics).  workspace: nerf_param_act_workspace(kind, M, N) bytes.
+ * accumulate: grad_p += result.  M == 0: nothing to do (the backward zeroes the gradients unless
+ * accumulate); N == 0: nothing to do.
+ * ------------------------------------------------------------------------- */
+#define NERF_ACT_GABOR 1
+#define NERF_ACT_SARF 2
+size_t nerf_param_act_workspace(int32_t kind, int64_t M, int32_t N);
+int nerf_param_act_fwd(int32_t kind, const float* z, int64_t ld_z, const float* p0, const float* p1, int64_t M,
+                       int32_t N, float* y, int64_t ld_y, void* stream);
+int nerf_param_act_bwd(int32_t kind, const float* grad_y, int64_t ld_g, const float* z, int64_t ld_z,
+                       const float* p0, const float* p1, int64_t M, int32_t N, float* grad_z, int64_t ld_dz,
+                       float* grad_p0, float* grad_p1, int32_t accumulate, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* Split-precision linear layer with a Gabor / Sarf activation in its epilogue: nerf_linear_gauss_x3
+ * for the kinds above, every element formula and rounding as nerf_param_act_fwd / _bwd.
+ *   mode NERF_GAUSS_FWD: z = A W^T + bias -> out, y = act(z) -> y (row stride ld_y).
+ *   mode NERF_GAUSS_BWD: g = A W^T (bias must be NULL), z = this layer's pre-activation;
+ *     out = grad_z; grad_p0 / grad_p1 (+)= the column sums, formed per 256-row tile in fp64 in a
+ *     fixed order, one partial plane per parameter, the tiles summed in a fixed order
+ *     (deterministic).  workspace: nerf_linear_act_workspace(kind, M, N) bytes.
+ * Forward layers wider than 256 outputs run as column blocks of <= 256.  The backward exists for
+ * N <= 128 only: on the 256-column tile its epilogue needs more registers than the kernel has (it
+ * would spill to scratch), so NERF_GAUSS_BWD with N > 128 returns NERF_ERR_UNSUPPORTED.  Requires
+ * N % 4 == 0 and 16-byte aligned out / y / z / bias / parameter rows (row strides multiples of 4);
+ * returns NERF_ERR_UNSUPPORTED otherwise (callers then use nerf_linear_fwd_x3 +
+ * nerf_param_act_fwd / _bwd). */
+size_t nerf_linear_act_workspace(int32_t kind, int64_t M, int32_t N);
+int nerf_linear_act_x3(int32_t kind, const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw,
+                       int32_t N, const float* bias, float* out, int64_t ldo, int32_t mode, const float* p0,
+                       const float* p1, float* y, int64_t ld_y, const float* z, int64_t ld_z, float* grad_p0,
+                       float* grad_p1, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fused Adam step (the optimizer of every reference experiment: torch.optim.Adam(eps=1e-5),
  * barf/model_interpolation.py:543-584) for up to NERF_ADAM_MAX_TENSORS tensors in ONE launch.
  * Per element, in torch's fp32 operation order:

@@ -26,6 +26,7 @@
 // vectors per plane (ds_write_b128).  Layers with N, K <= 256 take one 256 x 256 tile whose
 // operands stream through an LDS-DMA ring (linear_wgrad_x3_stream_kernel).
 #include "common.h"
+#include "param_act.h"
 
 using namespace nerf;
 
@@ -133,6 +134,15 @@ struct NTArgs {
     const float* gs; float* y2; int64_t ldy2; double* part;
 };
 
+// Gabor / Sarf epilogues (nerf_linear_act_x3): gs = the first parameter; the second parameter and
+// its partial plane (Gabor's spread).  A type of its own, so the kernels that take NTArgs keep
+// their argument layout.
+struct NTActArgs : NTArgs {
+    const float* gs1; double* part1;
+};
+template <int ACT> struct NTArgsSel { typedef NTActArgs T; };
+template <> struct NTArgsSel<0> { typedef NTArgs T; };
+
 // Gaussian activation (garf/gaussian.py:8-31) on a column quad, with exactly the element
 // formulas of gauss.hip: v = s^2 + 1e-6, y = exp((-(z*z)) * v); backward ge = g * exp((-(z*z)) v),
 // dz = (((-ge) * 2) * z) * v, column partial += (double)((-ge) * z^2).
@@ -167,6 +177,33 @@ __device__ __forceinline__ void gauss_bwd_store(float* o, f4 g, f4 z, f4 v, doub
     dz.y = gauss_bwd1(g.y, z.y, v.y, acc[1]);
     dz.z = gauss_bwd1(g.z, z.z, v.z, acc[2]);
     dz.w = gauss_bwd1(g.w, z.w, v.w, acc[3]);
+    __builtin_nontemporal_store(dz, reinterpret_cast<f4*>(o));
+}
+
+// Gabor / Sarf activations (param_act.h) on a column quad: the element functions of the
+// stand-alone kernels, quad loads and stores as the Gaussian ones above.
+template <int ACT> struct ActSel { typedef GaborFn Fn; };
+template <> struct ActSel<NERF_ACT_SARF> { typedef SarfFn Fn; };
+
+template <class Fn>
+__device__ __forceinline__ void act_fwd_store(float* o, float* yo, f4 z, const typename Fn::P (&k)[4]) {
+    __builtin_nontemporal_store(z, reinterpret_cast<f4*>(o));
+    f4 y;
+    y.x = Fn::fwd(z.x, k[0]);
+    y.y = Fn::fwd(z.y, k[1]);
+    y.z = Fn::fwd(z.z, k[2]);
+    y.w = Fn::fwd(z.w, k[3]);
+    __builtin_nontemporal_store(y, reinterpret_cast<f4*>(yo));
+}
+
+template <class Fn>
+__device__ __forceinline__ void act_bwd_store(float* o, f4 g, f4 z, const typename Fn::P (&k)[4], double (&a0)[4],
+                                              double (&a1)[4]) {
+    f4 dz;
+    dz.x = Fn::bwd(g.x, z.x, k[0], a0[0], a1[0]);
+    dz.y = Fn::bwd(g.y, z.y, k[1], a0[1], a1[1]);
+    dz.z = Fn::bwd(g.z, z.z, k[2], a0[2], a1[2]);
+    dz.w = Fn::bwd(g.w, z.w, k[3], a0[3], a1[3]);
     __builtin_nontemporal_store(dz, reinterpret_cast<f4*>(o));
 }
 
@@ -409,8 +446,10 @@ typedef __attribute__((address_space(1))) void glb_void_t;
 
 __device__ __forceinline__ int swz128(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
 
-template <int EPI, int JN>
-__global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(NTArgs a, int ntiles) {
+// ACT: 0 = the Gaussian activation for the NERF_EPI_GAUSS / _GAUSS_BWD epilogues, NERF_ACT_GABOR /
+// NERF_ACT_SARF = that activation in their place (compile-time: no branch in the epilogue loop).
+template <int EPI, int JN, int ACT = 0>
+__global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTArgsSel<ACT>::T a, int ntiles) {
     constexpr int BM = 256, BN = 128 * JN;
     constexpr int ABYTES = BM * 128, WBYTES = BN * 128;
     constexpr int LW = 8;                       // waves issuing the DMA (all; a 4/4 loader/storer split measured slower)
@@ -571,8 +610,17 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(NTArgs a, int
     if ((EPI & NERF_EPI_BIAS) && a.vec_ok && en + 4 <= a.N) bias4 = *reinterpret_cast<const f4*>(a.bias + en);
     constexpr bool GF = (EPI & NERF_EPI_GAUSS) != 0, GB = (EPI & NERF_EPI_GAUSS_BWD) != 0;
     f4 gv4 = f4{0.f, 0.f, 0.f, 0.f};
-    if ((GF || GB) && en + 4 <= a.N) gv4 = gauss_v4(a.gs, en);
+    if (ACT == 0 && (GF || GB) && en + 4 <= a.N) gv4 = gauss_v4(a.gs, en);
     double gp[4] = {0.0, 0.0, 0.0, 0.0};          // GB: this thread's column-quad partials of the tile
+    typedef typename ActSel<ACT>::Fn ActFn;
+    typename ActFn::P kp[4] = {};                 // ACT != 0: the quad's activation parameters
+    double gq[4] = {0.0, 0.0, 0.0, 0.0};          // ACT != 0, GB: partials of the second parameter
+    if constexpr (ACT != 0) {
+        if ((GF || GB) && en + 4 <= a.N) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) kp[e] = ActFn::load(a.gs, a.gs1, en + e);
+        }
+    }
     const EpiOut E{a.out, a.ldo, a.bias, a.aux, a.ldaux, a.M, a.N,
                    EPI | (a.epi & (NERF_EPI_MASKBITS | NERF_EPI_MASKOUT)), a.vec_ok};
     const bool mbits = (a.epi & NERF_EPI_MASKBITS) != 0, mout = (a.epi & NERF_EPI_MASKOUT) != 0;
@@ -654,9 +702,13 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(NTArgs a, int
                     if (ok && vec && GF) {
                         // pre-activation to out (kept for the backward), activation to y2
                         if (EPI & NERF_EPI_BIAS) v += bias4;
-                        gauss_fwd_store(a.out + (int64_t)m * a.ldo + en, a.y2 + (int64_t)m * a.ldy2 + en, v, gv4);
+                        if constexpr (ACT == 0)
+                            gauss_fwd_store(a.out + (int64_t)m * a.ldo + en, a.y2 + (int64_t)m * a.ldy2 + en, v, gv4);
+                        else
+                            act_fwd_store<ActFn>(a.out + (int64_t)m * a.ldo + en, a.y2 + (int64_t)m * a.ldy2 + en, v, kp);
                     } else if (ok && vec && GB) {
-                        gauss_bwd_store(a.out + (int64_t)m * a.ldo + en, v, xa[u], gv4, gp);
+                        if constexpr (ACT == 0) gauss_bwd_store(a.out + (int64_t)m * a.ldo + en, v, xa[u], gv4, gp);
+                        else act_bwd_store<ActFn>(a.out + (int64_t)m * a.ldo + en, v, xa[u], kp, gp, gq);
                     } else if (ok && vec) {
                         float* o = a.out + (int64_t)m * a.ldo + en;
                         if (EPI & NERF_EPI_BIAS) v += bias4;
@@ -704,6 +756,21 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(NTArgs a, int
             barrier();
 #pragma unroll
             for (int e = 0; e < 4; ++e) gp[e] = 0.0;
+            if constexpr (ACT != 0 && ActFn::kParams > 1) {
+                // the second parameter's plane, the same way
+#pragma unroll
+                for (int e = 0; e < 4; ++e) R[erow * BN + en + e] = gq[e];
+                barrier();
+                if (t < BN && t < a.N) {
+                    double sum = 0.0;
+#pragma unroll
+                    for (int r = 0; r < RS; ++r) sum += R[r * BN + t];
+                    a.part1[(int64_t)c_tile * a.N + t] = sum;
+                }
+                barrier();
+#pragma unroll
+                for (int e = 0; e < 4; ++e) gq[e] = 0.0;
+            }
         }
     };
 
@@ -2033,6 +2100,104 @@ extern "C" int nerf_linear_gauss_x3(const nerf_seg* segs, int32_t n_segs, int64_
     NERF_CHECK_LAUNCH();
     if (fwd) return NERF_OK;
     return nerf::gauss_reduce(part, slabs, N, inv_std, grad_inv_std, accumulate, part + slabs * N, st);
+}
+
+extern "C" size_t nerf_linear_act_workspace(int32_t kind, int64_t M, int32_t N) {
+    if ((kind != NERF_ACT_GABOR && kind != NERF_ACT_SARF) || M <= 0 || N <= 0) return 0;
+    // one fp64 row per 256-row tile and learnable parameter + the reduction's chunk sums
+    return (size_t)(kind == NERF_ACT_GABOR ? 2 : 1) * (size_t)((M + 255) / 256) * (size_t)N * sizeof(double) +
+           nerf::gauss_reduce_scratch(N);
+}
+
+template <int ACT>
+static void launch_act_glds(int epi, int nb, dim3 g3, dim3 b3, hipStream_t st, const NTActArgs& b, int ntiles) {
+#define NERF_ACT_LAUNCH(E)                                                                                \
+    do {                                                                                                 \
+        if (nb > 128) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 2, ACT>), g3, b3, 0, st, b, ntiles); \
+        else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 1, ACT>), g3, b3, 0, st, b, ntiles);         \
+    } while (0)
+    if (epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) NERF_ACT_LAUNCH(NERF_EPI_GAUSS | NERF_EPI_BIAS);
+    else if (epi == NERF_EPI_GAUSS) NERF_ACT_LAUNCH(NERF_EPI_GAUSS);
+    // the backward exists for 128-column tiles only (nerf_linear_act_x3 refuses wider ones)
+    else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS_BWD, 1, ACT>), g3, b3, 0, st, b, ntiles);
+#undef NERF_ACT_LAUNCH
+}
+
+extern "C" int nerf_linear_act_x3(int32_t kind, const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x,
+                                  int32_t ldw, int32_t N, const float* bias, float* out, int64_t ldo, int32_t mode,
+                                  const float* p0, const float* p1, float* y, int64_t ld_y, const float* z,
+                                  int64_t ld_z, float* grad_p0, float* grad_p1, int32_t accumulate, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    NERF_REQUIRE(kind == NERF_ACT_GABOR || kind == NERF_ACT_SARF);
+    const bool two = kind == NERF_ACT_GABOR;
+    NERF_REQUIRE(M >= 0 && M < (1ll << 31) && N >= 1 && (mode == NERF_GAUSS_FWD || mode == NERF_GAUSS_BWD));
+    NERF_REQUIRE(p0 != nullptr && (!two || p1 != nullptr) && out != nullptr);
+    const bool fwd = mode == NERF_GAUSS_FWD;
+    if (fwd) NERF_REQUIRE(y != nullptr && ld_y >= N);
+    else NERF_REQUIRE(bias == nullptr && z != nullptr && ld_z >= N && grad_p0 != nullptr &&
+                      (!two || grad_p1 != nullptr));
+    hipStream_t st = as_stream(stream);
+    if (M == 0) {
+        if (!fwd && !accumulate) {
+            if (hipMemsetAsync(grad_p0, 0, (size_t)N * sizeof(float), st) != hipSuccess) return NERF_ERR_LAUNCH;
+            if (two && hipMemsetAsync(grad_p1, 0, (size_t)N * sizeof(float), st) != hipSuccess)
+                return NERF_ERR_LAUNCH;
+        }
+        return NERF_OK;
+    }
+    // whole 16-byte quads everywhere, or the caller takes the unfused path
+    if ((N % 4) != 0 || !aligned16(out) || (ldo % 4) != 0 || ldo < N || !aligned16(p0) || (two && !aligned16(p1)) ||
+        (bias && !aligned16(bias)) || (fwd && (!aligned16(y) || (ld_y % 4) != 0)) ||
+        (!fwd && (!aligned16(z) || (ld_z % 4) != 0)))
+        return NERF_ERR_UNSUPPORTED;
+    // the backward epilogue on the 256-column tile needs more registers than the kernel has
+    // (it would spill to scratch): those layers take the separate activation pass
+    if (!fwd && N > 128) return NERF_ERR_UNSUPPORTED;
+    if (!fwd && (workspace == nullptr || workspace_bytes < nerf_linear_act_workspace(kind, M, N) ||
+                 (reinterpret_cast<uintptr_t>(workspace) & 7) != 0))
+        return NERF_ERR_WORKSPACE;
+    SegList L;
+    NERF_REQUIRE(build_segs(segs, n_segs, L));
+    NERF_REQUIRE(W_x && aligned16(W_x) && ldw == L.ktot && (ldw % BK) == 0);
+    const int epi = fwd ? (NERF_EPI_GAUSS | (bias ? NERF_EPI_BIAS : 0)) : NERF_EPI_GAUSS_BWD;
+    // 256-row tiles; column blocks of <= 256 (one for N <= 256), block n0's fp64 partials in their
+    // own [tiles][nb] slab block at plane + n0 * tiles, one plane per parameter
+    const int ntiles = (int)((M + 255) / 256);
+    const size_t plane = (size_t)ntiles * (size_t)N;
+    double* part = static_cast<double*>(workspace);
+    NTActArgs a{{L, (int)M, reinterpret_cast<const __bf16*>(W_x), ldw, N, bias, out, ldo, epi, z, ld_z, 1,
+                 p0, y, ld_y, part}, p1, part ? part + plane : nullptr};
+    int grid = cu_count_x3();
+    if (grid > ntiles) grid = ntiles;
+    const dim3 g3((unsigned)grid), b3(512);
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        NTActArgs b = a;
+        b.N = N - n0 < 256 ? N - n0 : 256;
+        b.Wx = a.Wx + (size_t)n0 * 2 * ldw;
+        b.bias = bias ? bias + n0 : nullptr;
+        b.out = out + n0;
+        b.gs = p0 + n0;
+        b.gs1 = two ? p1 + n0 : nullptr;
+        if (fwd) {
+            b.y2 = y + n0;
+        } else {
+            b.aux = z + n0;
+            b.part = part + (size_t)n0 * ntiles;
+            b.part1 = part + plane + (size_t)n0 * ntiles;
+        }
+        if (two) launch_act_glds<NERF_ACT_GABOR>(epi, b.N, g3, b3, st, b, ntiles);
+        else launch_act_glds<NERF_ACT_SARF>(epi, b.N, g3, b3, st, b, ntiles);
+        NERF_CHECK_LAUNCH();
+    }
+    if (fwd) return NERF_OK;
+    double* scratch = part + (two ? 2 : 1) * plane;
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        const int nb = N - n0 < 256 ? N - n0 : 256;
+        const int rc = nerf::param_act_reduce(kind, part + (size_t)n0 * ntiles, (int64_t)plane, ntiles, nb, p0 + n0,
+                                              grad_p0 + n0, two ? grad_p1 + n0 : nullptr, accumulate, scratch, st);
+        if (rc != NERF_OK) return rc;
+    }
+    return NERF_OK;
 }
 
 // NERF_WGRAD_SMALLN=0: layers with N <= 16 on the 128-tile kernel (A/B switch, read once)

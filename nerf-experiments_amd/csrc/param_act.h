@@ -1,0 +1,119 @@
+// Per-element formulas of the learnable per-channel activations next to GARF's Gaussian:
+//   Gabor  gaborf/gabor.py:8-64   (GaborActivation autograd, GaborAct)
+//   Sarf   sarf/activation.py:40-65 (SarfAct.forward, the cos * exp form it returns)
+// The stand-alone kernels (param_act.hip) and the GEMM epilogues (linear_x3.hip) call the same
+// functions, so the two routes differ only in the summation order of the column partials.
+//
+// Gabor, v = s^2 + 1e-6 (s = inv_standard_deviation, p = spread):
+//   forward   y  = exp((-(z*z)) * v) * cos(p*z)
+//   backward  go = (-exp((-(z*z)) * v)) * g
+//             dz = go * (((2*cos(pz)) * v) * z + p * sin(pz))
+//             dv_n = sum_m (go * z^2) * cos(pz)      ds_n = dv_n * (2 * s_n)
+//             dp_n = sum_m (go * z) * sin(pz)
+// Sarf, t = |z| + 1e-4, u = t^2, q = u + 1/(f*f), a = f/q (f = frequency, f != 0):
+//   forward   y  = cos(a) * exp(-u)
+//   backward  dz = g * (exp(-u) * ((sin(a)*f)/(q*q) - cos(a))) * (2 * t * sign(z)),  sign(+-0) = 0
+//             df_n = sum_m g * ((-sin(a)) * exp(-u)) * (1/q + 2/((f*f)*(q*q)))
+// f == 0 is outside the contract (1/(f*f) is infinite; the reference's own gradient is not
+// finite there).  sin / cos through sincos_enc (common.h), exp through expf, IEEE divisions.
+//
+// The sin / cos argument carries its rounding error along (sincos_arg): one fp32 ulp of p z (up to
+// ~25) or of f / q (up to ~8) is 5e-7 .. 2e-6, and it enters y undamped, where the Gaussian has a
+// single exp whose argument error is relative to y.  Gabor takes the exact product p z as
+// hi + lo (one FMA); Sarf forms t, q and f / q in fp64 and splits the quotient.  Everything else
+// is fp32 arithmetic in the order written above.
+#pragma once
+#include "common.h"
+
+namespace nerf {
+
+// sin and cos of hi + lo, |lo| <= ulp(hi) / 2: sincos_enc(hi) and the first-order term in lo
+// (the second-order term is below 1e-12).
+__device__ __forceinline__ void sincos_arg(float hi, float lo, float* s, float* c) {
+    float s0, c0;
+    sincos_enc(hi, &s0, &c0);
+    *s = __builtin_fmaf(c0, lo, s0);
+    *c = __builtin_fmaf(-s0, lo, c0);
+}
+
+struct GaborFn {
+    static constexpr int kKind = NERF_ACT_GABOR;
+    static constexpr int kParams = 2;
+    struct P { float v, p; };
+    static __device__ __forceinline__ P load(const float* p0, const float* p1, int n) {
+#pragma clang fp contract(off)
+        const float sv = p0[n];
+        return P{sv * sv + 1e-6f, p1[n]};
+    }
+    static __device__ __forceinline__ float fwd(float z, P k) {
+#pragma clang fp contract(off)
+        float s, c;
+        const float a = k.p * z;
+        sincos_arg(a, __builtin_fmaf(k.p, z, -a), &s, &c);
+        return expf((-(z * z)) * k.v) * c;
+    }
+    static __device__ __forceinline__ float bwd(float g, float z, P k, double& a0, double& a1) {
+#pragma clang fp contract(off)
+        float s, c;
+        const float a = k.p * z;
+        sincos_arg(a, __builtin_fmaf(k.p, z, -a), &s, &c);
+        const float z2 = z * z;
+        const float go = (-expf((-z2) * k.v)) * g;
+        a0 += (double)((go * z2) * c);
+        a1 += (double)((go * z) * s);
+        return go * ((((2.0f * c) * k.v) * z) + k.p * s);
+    }
+};
+
+struct SarfFn {
+    static constexpr int kKind = NERF_ACT_SARF;
+    static constexpr int kParams = 1;
+    struct P { float f, r; double rd; };          // frequency, 1 / (f * f) in fp32 and in fp64
+    static __device__ __forceinline__ P load(const float* p0, const float*, int n) {
+#pragma clang fp contract(off)
+        const float f = p0[n];
+        return P{f, 1.0f / (f * f), 1.0 / ((double)f * (double)f)};
+    }
+    // sin and cos of a = f / ((|z| + 1e-4)^2 + 1 / f^2), the quotient formed in fp64
+    static __device__ __forceinline__ void sincos_a(float z, P k, float* s, float* c) {
+#pragma clang fp contract(off)
+        const double td = (double)fabsf(z) + 1e-4;
+        const double ad = (double)k.f / (td * td + k.rd);
+        const float a = (float)ad;
+        sincos_arg(a, (float)(ad - (double)a), s, c);
+    }
+    static __device__ __forceinline__ float fwd(float z, P k) {
+#pragma clang fp contract(off)
+        const float t = fabsf(z) + 1e-4f;
+        const float u = t * t;
+        float s, c;
+        sincos_a(z, k, &s, &c);
+        return c * expf(-u);
+    }
+    static __device__ __forceinline__ float bwd(float g, float z, P k, double& a0, double&) {
+#pragma clang fp contract(off)
+        const float t = fabsf(z) + 1e-4f;
+        const float u = t * t;
+        const float q = u + k.r;
+        const float q2 = q * q;
+        float s, c;
+        sincos_a(z, k, &s, &c);
+        const float e = expf(-u);
+        const float sg = z > 0.0f ? 1.0f : (z < 0.0f ? -1.0f : 0.0f);
+        a0 += (double)(g * (((-s) * e) * (1.0f / q + 2.0f / ((k.f * k.f) * q2))));
+        return (g * (e * ((s * k.f) / q2 - c))) * ((2.0f * t) * sg);
+    }
+};
+
+// Column sums of per-slab fp64 partials [slabs][N] as nerf::gauss_reduce forms them (same two
+// fixed-order levels, same scratch), finished without the chain-rule factor:
+// dp_n (+)= (float)(sum_i partial[i][n]).  For Gabor's spread and Sarf's frequency.
+int param_reduce_plain(const double* partial, int64_t slabs, int N, float* dp, int accumulate, double* scratch,
+                       hipStream_t stream);
+
+// Both parameter gradients of one activation from its partial planes (plane p at
+// partial + p * plane): Gabor's s through nerf::gauss_reduce, the others through the plain sum.
+int param_act_reduce(int kind, const double* partial, int64_t plane, int64_t slabs, int N, const float* p0,
+                     float* grad_p0, float* grad_p1, int accumulate, double* scratch, hipStream_t stream);
+
+}  // namespace nerf

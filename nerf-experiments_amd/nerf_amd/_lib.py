@@ -47,6 +47,8 @@ NERF_KABSCH_MAX_POINTS = 4096
 NERF_PROP_MAX_EDGES = 512
 NERF_GAUSS_FWD = 0
 NERF_GAUSS_BWD = 1
+NERF_ACT_GABOR = 1
+NERF_ACT_SARF = 2
 
 
 class NerfSeg(ctypes.Structure):
@@ -207,6 +209,14 @@ _SIGNATURES = {
     "nerf_gauss_act_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "nerf_gauss_act_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i32,
                                    c_vp, c_sz, c_vp]),
+    "nerf_param_act_workspace": (c_sz, [c_i32, c_i64, c_i32]),
+    "nerf_param_act_fwd": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "nerf_param_act_bwd": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp,
+                                   c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "nerf_linear_act_workspace": (c_sz, [c_i32, c_i64, c_i32]),
+    "nerf_linear_act_x3": (c_i32, [c_i32, ctypes.POINTER(NerfSeg), c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
+                                   c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
+                                   c_sz, c_vp]),
     "nerf_linear_fwd": (c_i32, [ctypes.POINTER(NerfSeg), c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64,
                                 c_i32, c_vp, c_i64, c_vp]),
     "nerf_linear_wgrad_workspace": (c_sz, [c_i64, c_i32, c_i32]),

@@ -404,6 +404,48 @@ def gauss_act_bwd(grad_y: torch.Tensor, z: torch.Tensor, N: int, inv_std: torch.
     _lib.check(st, "nerf_gauss_act_bwd")
 
 
+# ------------------------------------------------------------- Gabor / Sarf activations (param_act.hip)
+# kind: _lib.NERF_ACT_GABOR (params = (inv_standard_deviation, spread)) or _lib.NERF_ACT_SARF
+# (params = (frequency,)); the gradients come in the same order
+_ACT_PARAMS = {_lib.NERF_ACT_GABOR: 2, _lib.NERF_ACT_SARF: 1}
+
+
+def _act_ptrs(kind: int, params, what: str = "activation parameters"):
+    if kind not in _ACT_PARAMS or len(params) != _ACT_PARAMS[kind]:
+        raise ValueError(f"{what}: kind {kind} takes {_ACT_PARAMS.get(kind)} tensors, got {len(params)}")
+    for p in params:
+        _require_cuda_f32(what, p)
+    return _ptr(params[0]), _ptr(params[1]) if len(params) > 1 else None
+
+
+def param_act_fwd(kind: int, z: torch.Tensor, N: int, params, y: torch.Tensor) -> None:
+    p0, p1 = _act_ptrs(kind, params)
+    end = TIMER.bracket("param_act_fwd", 0.0, 8.0 * z.shape[0] * N, fn="param_act_fwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_param_act_fwd(kind, _ptr(z), z.stride(0), p0, p1, z.shape[0], N, _ptr(y), y.stride(0),
+                                        _stream(z.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_param_act_fwd")
+
+
+def param_act_bwd(kind: int, grad_y: torch.Tensor, z: torch.Tensor, N: int, params, grad_z: torch.Tensor,
+                  grads, accumulate: bool = False) -> None:
+    M = z.shape[0]
+    lib = _lib.load()
+    p0, p1 = _act_ptrs(kind, params)
+    g0, g1 = _act_ptrs(kind, grads, "activation parameter gradients")
+    ws = torch.empty(max(1, (int(lib.nerf_param_act_workspace(kind, M, N)) + 7) // 8), device=z.device,
+                     dtype=torch.float64)
+    end = TIMER.bracket("param_act_bwd", 0.0, 12.0 * M * N, fn="param_act_bwd_kernel") if TIMER is not None else None
+    st = lib.nerf_param_act_bwd(kind, _ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0), p0, p1, M, N,
+                                _ptr(grad_z), grad_z.stride(0), g0, g1, int(accumulate), _ptr(ws), ws.numel() * 8,
+                                _stream(z.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_param_act_bwd")
+
+
 # ----------------------------------------------------------------------------- linear layers
 def make_segs(segs: Sequence[tuple[torch.Tensor, int, int]]):
     """segs: (tensor, k, row_div) with k % 4 == 0 valid columns; the tensor's row
@@ -531,6 +573,40 @@ def linear_gauss_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch
     if st == _lib.NERF_ERR_UNSUPPORTED:
         return False
     _lib.check(st, "nerf_linear_gauss_x3")
+    return True
+
+
+def linear_act_x3(kind: int, segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.Tensor, params, *,
+                  bias: torch.Tensor | None = None, y: torch.Tensor | None = None, z: torch.Tensor | None = None,
+                  grads=None, w_row_offset: int = 0) -> bool:
+    """linear_gauss_x3 for the Gabor / Sarf activations (nerf_linear_act_x3): forward (y given)
+    out = z = x W^T + b, y = act(z); input gradient (z, grads given) out = dL/dz from the product
+    (= dL/dy), grads = the activation parameters' gradients.  Returns False when the shapes need
+    the unfused path (N % 4, alignment)."""
+    p0, p1 = _act_ptrs(kind, params)
+    arr = make_segs(segs)
+    off = w_row_offset * ldw * 2 * 2
+    fwd = y is not None
+    lib = _lib.load()
+    ws = None
+    g0 = g1 = None
+    if not fwd:
+        g0, g1 = _act_ptrs(kind, grads, "activation parameter gradients")
+        ws = torch.empty(max(1, (int(lib.nerf_linear_act_workspace(kind, M, N)) + 7) // 8), device=out.device,
+                         dtype=torch.float64)
+    nbytes = _segs_bytes(segs, M) + 4.0 * N * ldw + (8.0 * M * N if fwd else 12.0 * M * N)
+    end = TIMER.bracket("linear_act_x3" if fwd else "linear_act_bwd_x3", 2.0 * M * N * ldw, nbytes,
+                        fn="linear_nt_x3_glds_kernel", launches=(N + 255) // 256) \
+        if TIMER is not None else None
+    st = lib.nerf_linear_act_x3(kind, arr, len(segs), M, Wx.data_ptr() + off, ldw, N, _ptr(bias), _ptr(out),
+                                out.stride(0), _lib.NERF_GAUSS_FWD if fwd else _lib.NERF_GAUSS_BWD, p0, p1,
+                                _ptr(y), y.stride(0) if fwd else 0, _ptr(z), z.stride(0) if z is not None else 0,
+                                g0, g1, 0, _ptr(ws), ws.numel() * 8 if ws is not None else 0, _stream(out.device))
+    if end is not None:
+        end.record()
+    if st == _lib.NERF_ERR_UNSUPPORTED:
+        return False
+    _lib.check(st, "nerf_linear_act_x3")
     return True
 
 

@@ -321,7 +321,7 @@ def split_layers(plan, M: int, dir_rd: int) -> frozenset:
     cols = {li for li, _ in plan.column_outputs}
     out = set()
     for l, lp in enumerate(plan.layers[:-1]):
-        if lp.N > 256 or l in plan.outputs or l in cols or lp.gauss is not None or lp.tanh:
+        if lp.N > 256 or l in plan.outputs or l in cols or lp.pact or lp.tanh:
             continue
         readers = [(c, si) for c, cl in enumerate(plan.layers) for si, s in enumerate(cl.sources)
                    if s.kind == "act" and s.layer == l]
@@ -423,11 +423,15 @@ class LayerPlan:
     GARF Gaussian activation with learnable inverse std ``gauss`` (garf/gaussian.py:34-63;
     the pre-activation is kept for the backward), or none.  ``residual`` = index of an earlier
     layer whose output's first ``residual_cols`` columns are added to this layer's output
-    (RadianceNetwork's ``z1[:, :128] + z2[:, :128]``, garf/model_radiance.py:92)."""
+    (RadianceNetwork's ``z1[:, :128] + z2[:, :128]``, garf/model_radiance.py:92).
+    ``act`` = (kind, parameters) of a Gabor / Sarf activation (gaborf/gabor.py, sarf/activation.py:
+    ``_lib.NERF_ACT_GABOR`` with (inv_standard_deviation, spread), ``_lib.NERF_ACT_SARF`` with
+    (frequency,)); it takes the routes, precision handling and eligibility rules of ``gauss``."""
     module: nn.Linear
     sources: list[Source]
     relu: bool
     gauss: nn.Parameter | None = None
+    act: tuple[int, tuple[nn.Parameter, ...]] | None = None
     residual: int = -1
     residual_cols: int = 0
     tanh: bool = False     # tanh in the epilogue (2d-reconstruction/model.py:48-56); backward reads the output
@@ -441,6 +445,43 @@ class LayerPlan:
     Wt: torch.Tensor | None = None
     Wpx: torch.Tensor | None = None
     Wtx: torch.Tensor | None = None
+
+    def __post_init__(self):
+        if self.gauss is not None and self.act is not None:
+            raise ValueError("LayerPlan: gauss= and act= are exclusive")
+        # the learnable parameters of this layer's activation (Gaussian, Gabor or Sarf) in
+        # state-dict order; empty without one.  Such a layer keeps its pre-activation.
+        self.pact: tuple[nn.Parameter, ...] = ((self.gauss,) if self.gauss is not None
+                                               else tuple(self.act[1]) if self.act is not None else ())
+
+    def act_fwd(self, z, out):
+        """The activation as a separate pass: out = act(z)."""
+        if self.gauss is not None:
+            K.gauss_act_fwd(z, self.N, self.gauss, out)
+        else:
+            K.param_act_fwd(self.act[0], z, self.N, self.act[1], out)
+
+    def act_bwd(self, g, z, dz, grads):
+        """The activation's backward as a separate pass (dz may be g)."""
+        if self.gauss is not None:
+            K.gauss_act_bwd(g, z, self.N, self.gauss, dz, grads[0])
+        else:
+            K.param_act_bwd(self.act[0], g, z, self.N, self.act[1], dz, grads)
+
+    def linear_act_x3(self, segs, M, Wx, ldw, N, out, **kw) -> bool:
+        """A GEMM with this layer's activation (forward: y=) or its backward (z=, grads=) in the
+        epilogue; False when the shapes need the separate pass."""
+        if self.gauss is not None:
+            if "grads" in kw:
+                kw["grad_inv_std"] = kw.pop("grads")[0]
+            return K.linear_gauss_x3(segs, M, Wx, ldw, N, out, self.gauss, **kw)
+        return K.linear_act_x3(self.act[0], segs, M, Wx, ldw, N, out, self.act[1], **kw)
+
+    def bwd_epilogue_fits(self, n: int) -> bool:
+        """An input-gradient GEMM of n output columns can take this layer's activation backward in
+        its epilogue: more than 32 columns (the split-precision tile kernels), and for Gabor / Sarf
+        at most 128 (nerf_linear_act_x3 has no 256-column backward: it would spill registers)."""
+        return n > 32 and (self.act is None or n <= 128)
 
     def finalize(self, device):
         self.N = self.module.out_features
@@ -546,12 +587,12 @@ class MLPPlan:
         return [t for lp in self.layers for t in (lp.module.weight, lp.module.bias)]
 
     def params(self):
-        """Autograd inputs in a fixed order: per layer weight, bias (+ Gaussian inverse std)."""
+        """Autograd inputs in a fixed order: per layer weight, bias (+ the activation's
+        parameters: Gaussian inverse std; Gabor inverse std, spread; Sarf frequency)."""
         ps = []
         for lp in self.layers:
             ps += [lp.module.weight, lp.module.bias]
-            if lp.gauss is not None:
-                ps.append(lp.gauss)
+            ps += lp.pact
         return ps
 
 
@@ -639,10 +680,10 @@ class MLPFunction(torch.autograd.Function):
                 # Gaussian layers: the GEMM writes the pre-activation z (kept for the backward) and,
                 # in split precision, exp(-z^2 v) into the layer's output from the same epilogue;
                 # otherwise nerf_gauss_act_fwd applies the activation in a second pass
-                target = torch.empty_like(out) if lp.gauss is not None else out
-                if (GAUSS_EPILOGUE and lp.gauss is not None and is_split(prec) and lp.N > 32 and lp.residual < 0
-                        and not lp.relu and K.linear_gauss_x3(segs, M, lp.Wpx, lp.Kp, lp.N, target, lp.gauss, bias=lp.module.bias,
-                                              y=out)):
+                target = torch.empty_like(out) if lp.pact else out
+                if (GAUSS_EPILOGUE and lp.pact and is_split(prec) and lp.N > 32 and lp.residual < 0
+                        and not lp.relu and lp.linear_act_x3(segs, M, lp.Wpx, lp.Kp, lp.N, target, bias=lp.module.bias,
+                                                             y=out)):
                     pre.append(target)
                     acts.append(out)
                     masks.append(None)
@@ -661,8 +702,8 @@ class MLPFunction(torch.autograd.Function):
                     target[:, :rc].copy_(acts[lp.residual][:, :rc])
                     epi |= NERF_EPI_ACCUM
                 lp.gemm(prec, segs, M, False, lp.N, lp.module.bias, target, epi, aux=mask)
-                if lp.gauss is not None:
-                    K.gauss_act_fwd(target, lp.N, lp.gauss, out)
+                if lp.pact:
+                    lp.act_fwd(target, out)
                     if lp.out_ld > lp.N:
                         out[:, lp.N:].zero_()
                     pre.append(target)
@@ -702,7 +743,7 @@ class MLPFunction(torch.autograd.Function):
         L = len(plan.layers)
         acts = list(saved[2:2 + L])
         pre_it = iter(saved[2 + L:])
-        pre = [next(pre_it) if lp.gauss is not None else None for lp in plan.layers]
+        pre = [next(pre_it) if lp.pact else None for lp in plan.layers]
         dev = pos.device
         dY: list[torch.Tensor | None] = [None] * L
         owned = [True] * L       # False: dY[i] is autograd's incoming tensor (never written in place)
@@ -731,7 +772,7 @@ class MLPFunction(torch.autograd.Function):
         dpos = None
         ddir = None
         layer_grads: list[list[torch.Tensor]] = [[] for _ in range(L)]
-        gauss_done: list[torch.Tensor | None] = [None] * L   # inverse-std gradients formed in an epilogue
+        gauss_done: list[list[torch.Tensor] | None] = [None] * L   # activation-parameter gradients formed in an epilogue
 
         # the input-gradient chain in one launch (csrc/mlp_fused.hip): every dY[l], l < L-1, from
         # the head gradient through the stored ReLU bits, when nothing else feeds the backward
@@ -831,17 +872,16 @@ class MLPFunction(torch.autograd.Function):
                     layer_grads[li] = [None, None]
                 else:
                     layer_grads[li] = [torch.zeros_like(w), torch.zeros_like(lp.module.bias)]
-                if lp.gauss is not None:
-                    layer_grads[li].append(torch.zeros_like(lp.gauss))
+                layer_grads[li] += [torch.zeros_like(p) for p in lp.pact]
                 continue
             gs = None
             if gauss_done[li] is not None:
                 gs = gauss_done[li]          # dY[li] already is dL/dz (the consumer's epilogue)
-            elif lp.gauss is not None:
-                # dY -> dZ through the Gaussian activation (+ the inverse-std gradient)
-                gs = torch.empty_like(lp.gauss)
+            elif lp.pact:
+                # dY -> dZ through the activation (+ its parameters' gradients)
+                gs = [torch.empty_like(p) for p in lp.pact]
                 dz = dZ if owned[li] else torch.empty_like(dZ)
-                K.gauss_act_bwd(dZ, pre[li], lp.N, lp.gauss, dz, gs)
+                lp.act_bwd(dZ, pre[li], dz, gs)
                 dZ = dz
             if lp.residual >= 0:
                 r, rc = lp.residual, lp.residual_cols
@@ -891,7 +931,7 @@ class MLPFunction(torch.autograd.Function):
                         sink.landed(w)
                         sink.landed(lp.module.bias)
                     gW = gb = None
-                layer_grads[li] = [gW, gb] + ([gs] if gs is not None else [])
+                layer_grads[li] = [gW, gb] + (gs if gs is not None else [])
             # ---- input gradients
             if chain:
                 continue
@@ -901,13 +941,13 @@ class MLPFunction(torch.autograd.Function):
                 if s.kind == "act":
                     j = s.layer
                     prod = plan.layers[j]
-                    if (GAUSS_EPILOGUE and prod.gauss is not None and plan.contributors[j] == 1 and dY[j] is None
-                            and not prod.relu and is_split(ctx.prec) and s.k_valid > 32):
+                    if (GAUSS_EPILOGUE and prod.pact and plan.contributors[j] == 1 and dY[j] is None
+                            and not prod.relu and is_split(ctx.prec) and prod.bwd_epilogue_fits(s.k_valid)):
                         # sole consumer: dL/dz of the Gaussian layer straight from this GEMM's epilogue
                         dz = torch.empty(M, prod.out_ld, device=dev, dtype=torch.float32)
-                        gsj = torch.empty_like(prod.gauss)
-                        if K.linear_gauss_x3(a_seg, M, lp.Wtx, lp.ldwt, s.k_valid, dz, prod.gauss, z=pre[j],
-                                             grad_inv_std=gsj, w_row_offset=koff):
+                        gsj = [torch.empty_like(p) for p in prod.pact]
+                        if prod.linear_act_x3(a_seg, M, lp.Wtx, lp.ldwt, s.k_valid, dz, z=pre[j], grads=gsj,
+                                              w_row_offset=koff):
                             dY[j] = dz
                             gauss_done[j] = gsj
                             continue
