@@ -729,6 +729,46 @@ int nerf_hashgrid_bwd_pos(const nerf_hashgrid_params* params, const float* x, co
                           size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * 2-D multiresolution hash grid (the Gigapixel image fit): INGPTable.forward / INGPEncoding.forward
+ * of 2d-ingp/model.py:13-115, pinned by tests/golden/hashgrid2d.npz and ingp2d.npz.  New entry
+ * points beside the 3-D ones (no ABI bump: nothing existing changes).  params: nerf_hashgrid_params
+ * with levels, table_size, features (1..8), res[] and primes[0..1]; normalize must be 0; query and
+ * primes[2] are ignored.  Level l's table has rows_l = (r+1)^2 rows when bijective ((r+1)^2 <=
+ * table_size) and table_size rows otherwise; table = [sum_l rows_l][features] fp32, levels back to
+ * back.  x: [n][2] fp32.
+ * Per level, fp32, no contraction: x_hat = x * r; corners floor(x_hat) + (0,0), (0,1), (1,0), (1,1)
+ * in that order; row = cx + (r+1) cy on the unclipped corner (bijective) or ((cx*pi1) ^ (cy*pi2))
+ * mod table_size in 64-bit integers (wrapping products, non-negative remainder); weight
+ * (1 - |x_hat_0 - cx|) * (1 - |x_hat_1 - cy|); out[n][l*F + f] = sum over the corners in order of
+ * w * table_l[row][f] (products rounded, then added).  Only those levels * features columns of the
+ * n rows of out (row stride out_ld) are written.
+ * Domain: points of [0,1)^2 never leave a table.  A bijective-level corner with cx or cy outside
+ * [0, r] (the reference raises or wraps there) contributes nothing, forward and backward, is never
+ * dereferenced, and sets bit 0 of *status (optional device int32, OR-ed, never cleared by the
+ * call).  Hashed levels are in range by construction and follow the formula for any coordinate.
+ * Status codes as the 3-D entry points (invalid params, out_ld / g_ld < levels * features, null
+ * pointers with n > 0: NERF_ERR_INVALID_ARG; a short workspace: NERF_ERR_WORKSPACE; a workspace not
+ * 256-byte aligned: NERF_ERR_INVALID_ARG), before any launch; n == 0 succeeds without a kernel (a
+ * non-accumulating nerf_hashgrid2d_bwd then clears grad_table with a memset when it is given).
+ * ------------------------------------------------------------------------- */
+/* Rows of level `level`'s table, or of the whole packed table when level < 0 (-1 on bad params). */
+int64_t nerf_hashgrid2d_table_rows(const nerf_hashgrid_params* params, int32_t level);
+int nerf_hashgrid2d_fwd(const nerf_hashgrid_params* params, const float* x, int64_t n, const float* table,
+                        float* out, int64_t out_ld, int32_t* status, void* stream);
+/* Gradient of sum(out * grad_out) w.r.t. the packed table; positions receive none.  Deterministic
+ * and reproducible bit for bit on a CPU: gmax = max |grad_out| over the [n][levels * features]
+ * block; non-finite gmax: every entry NaN; gmax == 0: s = 60; else with 4 * n * gmax < 2^e (frexp of
+ * the fp64 product (4.0 * n) * gmax) s = min(62 - e, 120).  Every in-domain corner adds
+ * llrint((double)w * ((double)g * 2^s)) to a 64-bit integer accumulator of its (row, f); then
+ * grad_table = (float)((double)acc * 2^-s), or += when accumulate.  workspace:
+ * nerf_hashgrid2d_workspace(params) bytes (0 on bad params), 256-byte aligned; it needs no zeroing
+ * by the caller and carries nothing between calls. */
+size_t nerf_hashgrid2d_workspace(const nerf_hashgrid_params* params);
+int nerf_hashgrid2d_bwd(const nerf_hashgrid_params* params, const float* x, int64_t n, const float* grad_out,
+                        int64_t g_ld, float* grad_table, int32_t accumulate, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Camera-pose alignment: CameraCalibrationModel.kabsch_algorithm
  * (barf/model_camera_calibration.py:69-156) and compute_pose_error (:340-345).
  * from, to: [n][3] fp32 device points, 3 <= n <= NERF_KABSCH_MAX_POINTS.  Writes R [3][3]

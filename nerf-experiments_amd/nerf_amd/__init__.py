@@ -12,6 +12,7 @@ from .model_gaborf import GaborAct  # noqa: F401
 from .model_sarf import SarfAct  # noqa: F401
 from .model_ingp import INGPEncoding, INGPTable, NaiveINGP, NerfModelINGP  # noqa: F401
 from .model_2d import FourierFeatures2d, Nerf2d  # noqa: F401
+from .model_ingp2d import Gigapixel  # noqa: F401  (its INGPTable / INGPEncoding stay in model_ingp2d)
 from .optim import FusedAdam  # noqa: F401
 from .pose import compute_pose_error, kabsch_algorithm, validation_transform_rays  # noqa: F401
 from .prop_sampler import PropNetEstimator, rendering  # noqa: F401

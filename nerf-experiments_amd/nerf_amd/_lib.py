@@ -269,6 +269,11 @@ _SIGNATURES = {
                                   c_vp, c_i64, c_vp, c_i32, c_vp, c_sz, c_vp]),
     "nerf_hashgrid_bwd_pos": (c_i32, [ctypes.POINTER(NerfHashgridParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32,
                                       c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "nerf_hashgrid2d_table_rows": (c_i64, [ctypes.POINTER(NerfHashgridParams), c_i32]),
+    "nerf_hashgrid2d_fwd": (c_i32, [ctypes.POINTER(NerfHashgridParams), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "nerf_hashgrid2d_workspace": (c_sz, [ctypes.POINTER(NerfHashgridParams)]),
+    "nerf_hashgrid2d_bwd": (c_i32, [ctypes.POINTER(NerfHashgridParams), c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp,
+                                    c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

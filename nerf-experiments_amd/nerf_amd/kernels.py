@@ -942,6 +942,83 @@ def hashgrid_bwd(params, grad_out: torch.Tensor, grad_table: torch.Tensor, works
     _lib.check(st, "nerf_hashgrid_bwd")
 
 
+# ----------------------------------------------------------------------------- 2-D hash grid (2d-ingp)
+def hashgrid2d_level_rows(resolution: int, table_size: int) -> int:
+    """Rows of one 2-D level's table: (r + 1)^2 when bijective, else table_size (nerf_hashgrid2d_table_rows)."""
+    n = (int(resolution) + 1) ** 2
+    return n if n <= table_size else table_size
+
+
+def hashgrid2d_table_rows(params) -> int:
+    return sum(hashgrid2d_level_rows(params.res[l], params.table_size) for l in range(params.levels))
+
+
+def _hashgrid2d_check(params, n: int, x: torch.Tensor, name: str, table: torch.Tensor, gname: str,
+                      rows_t: torch.Tensor) -> None:
+    if params.normalize != 0:
+        raise ValueError("the 2-D hash grid takes points already in [0, 1): params.normalize must be 0")
+    _require_cuda_f32("x", x)
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[1] != 2 or x.shape[0] < n:
+        raise ValueError(f"x must be a contiguous [>= {n}, 2] tensor (got {tuple(x.shape)})")
+    _require_cuda_f32(name, table)
+    rows = hashgrid2d_table_rows(params)
+    if not table.is_contiguous() or table.numel() != rows * params.features:
+        raise ValueError(f"{name} must be a contiguous packed table of {rows} x {params.features} floats "
+                         f"(got {tuple(table.shape)})")
+    _require_cuda_f32(gname, rows_t)
+    cols = params.levels * params.features
+    if rows_t.dim() != 2 or rows_t.shape[0] < n or rows_t.shape[1] < cols \
+            or (rows_t.numel() > 0 and rows_t.stride(1) != 1) or (rows_t.shape[0] > 1 and rows_t.stride(0) < cols):
+        raise ValueError(f"{gname} must be a row-major [>= {n}, >= {cols}] tensor (got {tuple(rows_t.shape)})")
+
+
+def hashgrid2d_fwd(params, table: torch.Tensor, out: torch.Tensor, x: torch.Tensor, n: int | None = None,
+                   status: torch.Tensor | None = None) -> None:
+    """nerf_hashgrid2d_fwd: out[:n, :levels * features] = the features of the points x [n, 2]; status: an
+    optional device int32 word whose bit 0 is set by a dropped out-of-domain corner."""
+    n = x.shape[0] if n is None else int(n)
+    _hashgrid2d_check(params, n, x, "table", table, "out", out)
+    if status is not None and (status.device != x.device or status.dtype != torch.int32 or status.numel() < 1):
+        raise ValueError("status must be a device int32 tensor")
+    cols = params.levels * params.features
+    end = TIMER.bracket("hashgrid2d_fwd", 0.0, 4.0 * n * cols * 4 + 4.0 * n * cols, fn="hashgrid2d_fwd_tile_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_hashgrid2d_fwd(ctypes.byref(params), x.data_ptr(), n, table.data_ptr(), out.data_ptr(),
+                                         out.stride(0) if out.shape[0] > 1 else out.shape[1], _ptr(status),
+                                         _stream(x.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_hashgrid2d_fwd")
+
+
+def hashgrid2d_workspace_bytes(params) -> int:
+    size = _lib.load().nerf_hashgrid2d_workspace(ctypes.byref(params))
+    if size == 0:
+        raise ValueError("invalid 2-D hash-grid parameters")
+    return int(size)
+
+
+def hashgrid2d_bwd(params, grad_out: torch.Tensor, grad_table: torch.Tensor, workspace: torch.Tensor,
+                   x: torch.Tensor, n: int | None = None, accumulate: bool = False) -> None:
+    """nerf_hashgrid2d_bwd: the deterministic fixed-point table gradient (positions receive none)."""
+    n = x.shape[0] if n is None else int(n)
+    _hashgrid2d_check(params, n, x, "grad_table", grad_table, "grad_out", grad_out)
+    need = hashgrid2d_workspace_bytes(params)
+    if workspace.device != x.device or not workspace.is_contiguous() \
+            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256:
+        raise ValueError(f"workspace must be a contiguous, 256-byte aligned device buffer of >= {need} bytes")
+    cols = params.levels * params.features
+    end = TIMER.bracket("hashgrid2d_bwd", 0.0, 4.0 * n * cols * 8 + 4.0 * n * cols, fn="nerf_hashgrid2d_bwd") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_hashgrid2d_bwd(ctypes.byref(params), x.data_ptr(), n, grad_out.data_ptr(),
+                                         grad_out.stride(0) if grad_out.shape[0] > 1 else grad_out.shape[1],
+                                         grad_table.data_ptr(), int(accumulate), workspace.data_ptr(),
+                                         workspace.numel() * workspace.element_size(), _stream(x.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_hashgrid2d_bwd")
+
+
 # ----------------------------------------------------------------------------- pose alignment
 def kabsch(p_from: torch.Tensor, p_to: torch.Tensor, remove_outliers: bool = True, error: bool = False):
     """nerf_kabsch: (R [3, 3], t [1, 3], c [] (, mean aligned distance [])) on the device."""
