@@ -503,6 +503,11 @@ int nerf_mlp_fused_render(const nerf_fused_layer* layers, int32_t n_layers, cons
  * layer with N > 256, with a column output or without an output buffer, with NERF_FUSED_BF16, and
  * for the input-gradient chain. */
 #define NERF_FUSED_SPLIT_OUT(l) (1 << (8 + (l)))
+/* NERF_FUSED_GENERIC (tests; no ABI bump, as above): every layer runs the kernels' generic chunk loop,
+ * also the plain layers (register-fed only, N a multiple of 32 and <= 256, ldo == N, an output buffer,
+ * no column / second output), which otherwise take a loop trimmed of the cases they never meet.  Same
+ * stores, same bits. */
+#define NERF_FUSED_GENERIC 2
 int nerf_mlp_fused_run(const nerf_fused_layer* layers, int32_t n_layers, const void* image, int64_t M,
                        const nerf_fused_encoding* encodings, const nerf_fused_composite* composite, int32_t flags,
                        void* stream);

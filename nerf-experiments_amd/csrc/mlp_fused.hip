@@ -108,6 +108,7 @@ struct FusedArgs {
     int span;          // tiles a workgroup runs back to back (2: rays of 256 samples), ntiles % span == 0
     int comp_on;       // forward: composite every tile's rays (nerf_mlp_fused_render)
     int split_mask;    // forward, split precision: bit l = layer l stores its output quad-split (nerf_amd.h)
+    int no_plain;      // NERF_FUSED_GENERIC: plain layers take the generic chunk loop too (tests)
     nerf_fused_composite comp;
     // a generated hash-grid encoding (params.kind 2): its parameters, table and level row offsets
     nerf_hashgrid_params hg;
@@ -291,6 +292,9 @@ __device__ __forceinline__ void issue_dma(Ctx& c, int slot) {
 #pragma unroll
     for (int i = 0; i < DMA_PER_WAVE; ++i) {
         const int u = (c.wave + NWAVE * i) & (c.d_units - 1);   // d_units: 8 or 16
+        // (both pieces' offsets precomputed per layer in dma_seek, a chunk adding only d_off and the
+        // slot, measured no faster on top of the plain loop: mip step 10.84-10.86 against 10.83-10.84 ms
+        // without, profiles/plain01/ab_vs_parent.txt — this form stays)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rimg, (lds_void_t*)(dst + u * 1024), 16, c.lane * 16,
                                                  c.d_off + u * 1024, 0, 0);
     }
@@ -807,6 +811,119 @@ __device__ __forceinline__ void epi_part(Ctx& c, LayerState& st, int p, int ch, 
     }
 }
 
+// Epilogue of chunk ch of a PLAIN layer (decided once per layer in fused_layer: register-fed only,
+// N a multiple of 32 and <= 256, dense output rows ldo == N, an output buffer, no column output,
+// no second output), the parts as in epi_part.  Every chunk exists, is fed forward, is in range of
+// its row and belongs to a pair, so none of epi_part's per-chunk range / case tests remain, and an
+// even chunk (EPAR 0) only stashes its values: no dropped store.  The odd chunk (EPAR 1) writes
+// the pair at the rows' offsets (OOB past M: dropped by the buffer) plus the scalar 64 (ch - 1).
+template <int MODE, int EPAR>
+__device__ __forceinline__ void epi_plain(Ctx& c, LayerState& st, int p, int ch, f4 (&a)[SB], f4 b) {
+    static_assert(EPAR == 0 || EPAR == 1, "compile-time parity");
+    const int q = ch >> 1;
+    constexpr int bb = EPAR;
+    if (p < 2) {
+        if (p >= SB) return;
+        const int sb = p;
+        f4& v = a[sb];
+        if constexpr (is_fwd(MODE)) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                v[r] = __builtin_bit_cast(float, max(__builtin_bit_cast(int, v[r] + b[r]), st.floor_i));
+            f4 sv = v;
+            if constexpr (is_qs(MODE)) {
+                if (st.qsplit) {
+                    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+                    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                    unsigned h0, l0, h1, l1;
+                    split2(v[0], v[1], h0, l0);
+                    split2(v[2], v[3], h1, l1);
+                    char* d = c.ximg + ((q * SB + sb) * 2) * 1024 + c.lane * 16 + 8 * bb;
+                    *reinterpret_cast<u2*>(d) = u2{h0, h1};
+                    *reinterpret_cast<u2*>(d + 1024) = u2{l0, l1};
+                    sv = __builtin_bit_cast(f4, u4{h0, h1, l0, l1});
+                }
+            }
+            if constexpr (EPAR == 0) {
+                st.stash[sb] = sv;
+            } else {
+                const int so = 64 * (ch - 1);
+                __builtin_amdgcn_raw_buffer_store_b128(st.stash[sb], st.ro, st.row_off[sb], so, ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(sv, st.ro, st.row_off[sb] + 64u, so, ST_AUX);
+            }
+        } else {
+            // the ReLU bits as in epi_part; word 1 from chunk 8 on (an even chunk)
+            const int sh = 4 * (7 - (ch & 7));
+            if constexpr (EPAR == 0) {
+                if (ch == 8) st.mcur[sb] = st.mi[sb][1];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int dead = __builtin_amdgcn_sbfe((int)st.mcur[sb], (unsigned)(sh + r), 1u);   // 0 / -1
+                const float x = v[r];
+                v[r] = __builtin_bit_cast(float, __builtin_bit_cast(int, x) & ~dead);
+            }
+            if constexpr (EPAR == 0) {
+                st.stash[sb] = v;
+            } else {
+                // pair_stores without the range select: pa / pb already carry the +64 of the lanes
+                // s >= 8, which write chunk ch in both stores (fused_layer)
+                const f4 x = st.stash[sb];
+                const bool lo8 = (c.lane & 8) == 0;
+                f4 rx, ry;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float xr = x[r], yr = v[r];
+                    rx[r] = ror8(xr);
+                    ry[r] = ror8(yr);
+                }
+                const f4 va = lo8 ? x : ry;
+                const f4 vb = lo8 ? rx : v;
+                const int so = 64 * (ch - 1);
+                __builtin_amdgcn_raw_buffer_store_b128(va, st.ro, st.pa[sb], so, ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(vb, st.ro, st.pb[sb], so, ST_AUX);
+            }
+        }
+    } else if (p == 2) {
+        if constexpr (is_fwd(MODE)) {
+#pragma unroll
+            for (int sb = 0; sb < SB; ++sb) {
+                unsigned t = st.mw[sb][1];
+#pragma unroll
+                for (int r = 3; r >= 0; --r) t = shift_in_dead(t, a[sb][r]);
+                st.mw[sb][1] = t;
+            }
+            if constexpr (EPAR == 1) {
+                if (ch == 7) {
+#pragma unroll
+                    for (int sb = 0; sb < SB; ++sb) {
+                        st.mw[sb][0] = st.mw[sb][1];
+                        st.mw[sb][1] = 0;
+                    }
+                }
+            }
+        }
+    } else {
+        if (!(is_qs(MODE) && st.qsplit)) {
+#pragma unroll
+            for (int sb = 0; sb < SB; ++sb) {
+                typedef unsigned u2 __attribute__((ext_vector_type(2)));
+                char* d = c.ximg + ((q * SB + sb) * 2) * 1024 + c.lane * 16 + 8 * bb;
+                if constexpr (is_x1(MODE)) {
+                    *reinterpret_cast<u2*>(d) = u2{hi2(a[sb][0], a[sb][1]), hi2(a[sb][2], a[sb][3])};
+                } else {
+                    unsigned h0, l0, h1, l1;
+                    split2(a[sb][0], a[sb][1], h0, l0);
+                    split2(a[sb][2], a[sb][3], h1, l1);
+                    const u2 h = {h0, h1}, lo = {l0, l1};
+                    *reinterpret_cast<u2*>(d) = h;
+                    *reinterpret_cast<u2*>(d + 1024) = lo;
+                }
+            }
+        }
+    }
+}
+
 // Epilogue parts in the MFMA stream: the parts that do anything (1 only with SB = 2) go to
 // consecutive register-fed stages from EPI0 on, part 3 (the hi/lo split into the next layer's
 // operand image) included; parts that do not fit run after the chunk's HBM-fed MFMAs
@@ -843,7 +960,9 @@ __device__ __forceinline__ void first_reads(bf16x8 (&fr)[FA][2], unsigned sa) {
 
 // One 16-row chunk's register-fed k-blocks (compile-time KB_I: immediate LDS offsets), fragments
 // read FA steps ahead; the previous chunk's epilogue parts 0-2 at stages EPI0 .. EPI0 + 2.
-template <int MODE, int KBR, int KBH, int KB_I, int EPAR = -1>
+// PL: a plain layer's chunk (epi_plain; EPAR 2: the layer's first chunk, which has no predecessor
+// and runs no epilogue and loads no bias)
+template <int MODE, int KBR, int KBH, int KB_I, int EPAR = -1, bool PL = false>
 __device__ __forceinline__ void reg_steps(Ctx& c, LayerState& st, unsigned sa, bf16x8 (&fr)[FA][2], f4 (&a)[SB],
                                           f4 (&pv)[SB], f4& pb, int ch) {
     constexpr int EPI0 = KBR >= 8 ? epi0_of<MODE>() : (KBR >= 4 ? 1 : 0);
@@ -874,12 +993,16 @@ __device__ __forceinline__ void reg_steps(Ctx& c, LayerState& st, unsigned sa, b
         }
         // (placing the epilogue parts of the two waves of a SIMD at different stages, 0-2 and 4-6,
         // measured slower: chain 3.78 -> 4.03-4.09 ms, forward 3.86 -> 3.94-4.00 per mip step)
-        if constexpr (KB_I == EPI0 && is_fwd(MODE))
+        if constexpr (KB_I == EPI0 && is_fwd(MODE) && !(PL && EPAR == 2))
             bias_wait<(KBR > 0 ? DMA_PER_WAVE : 0) + (is_x1(MODE) ? 1 : 2) * KBH>(pb);   // (younger: the DMA, the HBM fragments)
-        if constexpr (KB_I >= EPI0 && KB_I < EPI0 + epi_placed<KBR, EPI0>())
-            epi_part<MODE, EPAR>(c, st, epi_part_of(KB_I - EPI0), ch - 1, pv, pb);
+        if constexpr (KB_I >= EPI0 && KB_I < EPI0 + epi_placed<KBR, EPI0>()) {
+            if constexpr (!PL)
+                epi_part<MODE, EPAR>(c, st, epi_part_of(KB_I - EPI0), ch - 1, pv, pb);
+            else if constexpr (EPAR != 2)
+                epi_plain<MODE, EPAR>(c, st, epi_part_of(KB_I - EPI0), ch - 1, pv, pb);
+        }
         __builtin_amdgcn_sched_barrier(0);
-        reg_steps<MODE, KBR, KBH, KB_I + 1, EPAR>(c, st, sa, fr, a, pv, pb, ch);
+        reg_steps<MODE, KBR, KBH, KB_I + 1, EPAR, PL>(c, st, sa, fr, a, pv, pb, ch);
     }
 }
 
@@ -954,6 +1077,31 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
         }
     }
 
+    // A plain layer (decided here once, wave-uniform; never inside the chunk loop): register-fed
+    // only, N a multiple of 32 and <= 256 (an even count of <= 16 chunks, all fed forward and
+    // masked), dense output rows (ldo == N: every column in range), an output buffer, no column
+    // output (forward) / no second output (chain).  Its chunk loop runs epi_plain.  Diagnostic
+    // builds keep the generic loop.
+    bool plain = false;
+    if constexpr (KBR == 8 && KBH == 0) {
+        plain = NERF_TU_BUILD_FLAGS == 0 &&
+                *(const __attribute__((address_space(4))) int*)(c.kargs + offsetof(FusedArgs, no_plain)) == 0 &&
+                (N & 31) == 0 && N <= 32 * KBMAX && ldo == N &&
+                LF(fptr_t, out, l) != nullptr &&
+                (is_fwd(MODE) ? LF(fptr_t, col_out, l) == nullptr : LF(fptr_t, out2, l) == nullptr);
+        if constexpr (!is_fwd(MODE)) {
+            if (plain) {
+                // lanes s >= 8 write chunk ch of the pair (ch - 1, ch) in both stores (pair_stores)
+#pragma unroll
+                for (int sb = 0; sb < SB; ++sb) {
+                    const unsigned hi8 = (c.lane & 8) != 0 ? 64u : 0u;
+                    st.pa[sb] += hi8;
+                    st.pb[sb] += hi8;
+                }
+            }
+        }
+    }
+
     // ---- HBM-fed input blocks (encodings, gradients): lane (s, g) of block kh holds columns
     // 32 kh + 8 g .. +7 of its sample
     bf16x8 hh[KBH > 0 ? KBH : 1][SB], hl[KBH > 0 ? KBH : 1][SB];
@@ -1020,6 +1168,21 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
 
     // the previous chunk's accumulators (its epilogue runs during the current chunk)
     f4 pv[SB] = {};
+    // the last chunk's epilogue, after the loop (a plain layer's last chunk is odd)
+    auto last_epilogue = [&](auto pl_tag) __attribute__((always_inline)) {
+        f4 lb = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (is_fwd(MODE)) {
+            buf_load16(lb, st.bias_off + 64u * (unsigned)(NC - 1), c.rimg);
+            bias_wait<0>(lb);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            if constexpr (decltype(pl_tag)::value)
+                epi_plain<MODE, 1>(c, st, p, NC - 1, pv, lb);
+            else
+                epi_part<MODE>(c, st, p, NC - 1, pv, lb);
+        }
+    };
     if constexpr (KBR == 0) {
         // The first layer has no register-fed part and no DMA.  Its weight fragments (and biases)
         // come from L2 one chunk ahead through builtin buffer loads whose waits hipcc counts, so a
@@ -1072,23 +1235,29 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
             step(ch, hA, hB, bA, bB);
             if (ch + 1 < NC) step(ch + 1, hB, hA, bB, bA);
         }
+        last_epilogue(std::false_type{});
     } else
     {
-    // one chunk; EP: the compile-time parity of its predecessor (whose epilogue it runs)
-    auto chunk = [&](int ch, auto ep_tag) __attribute__((always_inline)) {
+    // one chunk; EP: the compile-time parity of its predecessor (whose epilogue it runs).  VM >= 0: a
+    // chunk of a plain layer (epi_plain; EP 2: its first chunk, no predecessor), VM = the vector-memory
+    // ops issued on that path after the chunk's DMA and before the wait below
+    auto chunk = [&](int ch, auto ep_tag, auto vm_tag) __attribute__((always_inline)) {
         constexpr int EP = decltype(ep_tag)::value;
+        constexpr int VM = decltype(vm_tag)::value;
+        constexpr bool PL = VM >= 0;
+        static_assert(!PL || (KBR == 8 && KBH == 0), "plain layers: register-fed only");
         // the previous chunk's biases (rows 4 g .. 4 g + 3), for its epilogue in this chunk, issued
         // before this chunk's DMA so that waiting for it does not wait for the DMA
         f4 pb = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (is_fwd(MODE))
-            buf_load16(pb, st.bias_off + 64u * (unsigned)(ch > 0 ? ch - 1 : 0), c.rimg);
+        if constexpr (is_fwd(MODE) && !(PL && EP == 2))
+            buf_load16(pb, st.bias_off + 64u * (unsigned)(PL || ch > 0 ? ch - 1 : 0), c.rimg);
         const unsigned sa = lds_addr(c.smem + c.cur * SLOT_BYTES + c.lane * 16);
         bf16x8 fr[FA][2];
         if constexpr (KBR > 0) {
             // this chunk's DMA share has landed (issued at the start of the previous register-fed
             // chunk and followed by >= after_dma_vm vector-memory ops), then everyone else's; the
             // other slot is free
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(after_dma_vm<MODE>()) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PL ? VM : after_dma_vm<MODE>()) : "memory");
 #ifndef NERF_FUSED_DIAG_NOBARRIER      // diagnostic builds only (timing without the per-chunk barrier)
             barrier();
 #endif
@@ -1109,7 +1278,7 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
         f4 a[SB];
 #pragma unroll
         for (int sb = 0; sb < SB; ++sb) a[sb] = f4{0.f, 0.f, 0.f, 0.f};
-        reg_steps<MODE, KBR, KBH, 0, EP>(c, st, sa, fr, a, pv, pb, ch);
+        reg_steps<MODE, KBR, KBH, 0, EP, PL>(c, st, sa, fr, a, pv, pb, ch);
         // the HBM-fed fragments have landed: with a register-fed part the 4 epilogue stores of parts
         // 0-1 were issued after them
 #pragma unroll
@@ -1134,7 +1303,9 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
         if constexpr (KBR == 0) bias_wait<0>(pb);
         // the parts the stages did not take (all of them for the first layer)
 #pragma unroll
-        for (int i = epi_placed<KBR, EPI0>(); i < EPI_NP; ++i) epi_part<MODE, EP>(c, st, epi_part_of(i), ch - 1, pv, pb);
+        for (int i = epi_placed<KBR, EPI0>(); i < EPI_NP; ++i) {
+            if constexpr (!PL) epi_part<MODE, EP>(c, st, epi_part_of(i), ch - 1, pv, pb);   // (plain: all placed)
+        }
         if constexpr (KBR > 0) c.cur ^= 1;
 #pragma unroll
         for (int sb = 0; sb < SB; ++sb) pv[sb] = a[sb];
@@ -1142,19 +1313,41 @@ __device__ __forceinline__ void fused_layer(Ctx& c, int l, int base) {
     // unrolled by two: chunk ch (even) runs the epilogue of the odd chunk ch - 1 (none for ch = 0:
     // its stores are dropped), chunk ch + 1 that of the even chunk ch — the pair-store parity, the
     // stash and the accumulator hand-over are compile-time, with no branch or register copy per chunk
-    for (int ch = 0; ch < NC; ch += 2) {
-        chunk(ch, std::integral_constant<int, 1>{});
-        if (ch + 1 < NC) chunk(ch + 1, std::integral_constant<int, 0>{});
-    }
-    }
-    {
-        f4 lb = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (is_fwd(MODE)) {
-            buf_load16(lb, st.bias_off + 64u * (unsigned)(NC - 1), c.rimg);
-            bias_wait<0>(lb);
+    auto generic_loop = [&]() __attribute__((always_inline)) {
+        for (int ch = 0; ch < NC; ch += 2) {
+            chunk(ch, std::integral_constant<int, 1>{}, std::integral_constant<int, -1>{});
+            if (ch + 1 < NC) chunk(ch + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, -1>{});
         }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) epi_part<MODE>(c, st, p, NC - 1, pv, lb);
+        last_epilogue(std::false_type{});
+    };
+    if constexpr (KBR == 8 && KBH == 0) {
+        if (plain) {
+            // The plain loop: an even chunk's epilogue only stashes, an odd chunk's issues the pair's two
+            // stores (epi_plain), so the counted wait at a chunk's start differs by parity.  After the
+            // DMA of chunk ch (issued at the start of chunk ch - 1) the wave issues the stores of
+            // chunk ch - 1's in-stream epilogue (that of chunk ch - 2: two if ch - 2 is odd, none if it
+            // is even or there is none) and, in the forward, the bias load at the start of chunk ch:
+            //   chunk 0      (no epilogue, no bias load): the previous layer's tail after its last
+            //                chunk's DMA: forward bias load + 2 stores + mask store, chain 2 stores
+            //                -> forward 3 (one to spare), chain 2
+            //   chunk 1, even chunks >= 2: forward 1 (the bias load), chain 0
+            //   odd chunks >= 3:           forward 3 (2 stores + the bias load), chain 2
+            // (vmcnt(0) in the chain's even chunks waits for nothing but the DMA it needs: every older
+            // store retires before it, in order.)  Chunks 0 and 1 are peeled for their counts.
+            constexpr int V_LO = is_fwd(MODE) ? 1 : 0, V_HI = is_fwd(MODE) ? 3 : 2;
+            chunk(0, std::integral_constant<int, 2>{}, std::integral_constant<int, V_HI>{});
+            chunk(1, std::integral_constant<int, 0>{}, std::integral_constant<int, V_LO>{});
+            for (int ch = 2; ch < NC; ch += 2) {
+                chunk(ch, std::integral_constant<int, 1>{}, std::integral_constant<int, V_LO>{});
+                chunk(ch + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, V_HI>{});
+            }
+            last_epilogue(std::true_type{});
+        } else {
+            generic_loop();
+        }
+    } else {
+        generic_loop();
+    }
     }
     if constexpr (is_fwd(MODE)) {
         // the lane's two mask words, each chunk's nibble at 4 (7 - (ch & 7)) whatever the chunk count
@@ -1538,7 +1731,7 @@ namespace {
 int fused_launch(const nerf_fused_layer* layers, int32_t n_layers, const void* image, int64_t M,
                  const nerf_fused_encoding* encodings, const nerf_fused_composite* comp, int32_t flags, void* stream) {
     const int split_mask = (int)(((uint32_t)flags >> 8) & 0xffffu);
-    NERF_REQUIRE((flags & ~(NERF_FUSED_BF16 | (0xffff << 8))) == 0);
+    NERF_REQUIRE((flags & ~(NERF_FUSED_BF16 | NERF_FUSED_GENERIC | (0xffff << 8))) == 0);
     const bool single_pass = (flags & NERF_FUSED_BF16) != 0;
     NERF_REQUIRE(layers != nullptr && image != nullptr);
     NERF_REQUIRE(n_layers >= 1 && n_layers <= NERF_FUSED_MAX_LAYERS);
@@ -1704,6 +1897,7 @@ int fused_launch(const nerf_fused_layer* layers, int32_t n_layers, const void* i
     // compositing fused into the forward (include/nerf_amd.h nerf_fused_composite)
     a.comp_on = 0;
     a.split_mask = split_mask;
+    a.no_plain = (flags & NERF_FUSED_GENERIC) != 0;
     memset(&a.comp, 0, sizeof(a.comp));
     if (comp != nullptr) {
         a.comp = *comp;

@@ -37,6 +37,7 @@ NERF_EPI_TANH = 4096
 NERF_EPI_TANH_BWD = 8192
 NERF_ERR_UNSUPPORTED = -2
 NERF_FUSED_BF16 = 1
+NERF_FUSED_GENERIC = 2
 
 
 def NERF_FUSED_SPLIT_OUT(layer: int) -> int:

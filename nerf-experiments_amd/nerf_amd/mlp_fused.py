@@ -45,9 +45,11 @@ def _flags(passes: int) -> int:
     """nerf_mlp_fused_run flags of a pass count (3: the 3 x bf16 split, 1: NERF_FUSED_BF16)."""
     if passes not in (1, 3):
         raise ValueError(f"fused MLP: passes must be 1 or 3 (got {passes})")
-    return _lib.NERF_FUSED_BF16 if passes == 1 else 0
+    return (_lib.NERF_FUSED_BF16 if passes == 1 else 0) | (_lib.NERF_FUSED_GENERIC if FORCE_GENERIC else 0)
 
 
+# tests: every layer through the kernels' generic chunk loop (NERF_FUSED_GENERIC), the plain ones too
+FORCE_GENERIC = False
 FUSED_TYPES = {(0, 1): 1, (0, 2): 2, (4, 0): 3, (8, 0): 6, (8, 1): 7, (8, 2): 8}   # (kbr, kbh) -> type
 ENABLED = os.environ.get("NERF_FUSED", "1") != "0"     # A/B switch (bench, tests)
 # a per-ray encoding read by a later layer comes from registers captured at the tile start; tests
