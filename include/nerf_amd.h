@@ -99,7 +99,9 @@ int nerf_composite_bwd(const float* density, int64_t density_stride,
 
 /* ---------------------------------------------------------------------------
  * Stratified / equidistant t sampling (a6) + _get_intervals.
- *   t_s = linspace(near, far - D, S)[s]  (D = (far-near)/S)
+ *   t_s = linspace(near, far - D, S)[s]  (D = (far-near)/S; far - D formed in double from the
+ *         fp32 near / far and rounded once, each element one fused multiply-add, as torch.linspace
+ *         on the reference's Python floats: bit-equal to it when near and far are fp32 values)
  *         + (stratified ? U_{r,s} * D : 0) + (offset != 0 ? U_r * D * offset : 0)
  *   t_start = t; t_end[s] = t[s+1], t_end[S-1] = far.
  * U are Philox-4x32-10 uniforms in [0,1) keyed by (seed, offset_counter).

@@ -199,13 +199,23 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t counter,
     return u32_to_unit(r.v[0]);
 }
 
-// torch.linspace(start, end, steps) element (CPU float kernel formula).
+// torch.linspace(start, end, steps) element: start + step * idx in the first half, end - step *
+// (steps - idx - 1) in the second, each as ONE fused multiply-add.  torch's kernels (x86 built for
+// FMA, and CUDA) contract the expression, so a separately rounded product is off by an ulp
+// wherever step * idx is not exact (tests/test_raypath_ref.py).
 __device__ __forceinline__ float linspace_at(float start, float end, int steps, int idx) {
 #pragma clang fp contract(off)
     if (steps == 1) return start;
     const float step = (end - start) / (float)(steps - 1);
     const int halfway = steps / 2;
-    return (idx < halfway) ? start + step * (float)idx : end - step * (float)(steps - idx - 1);
+    return (idx < halfway) ? __builtin_fmaf(step, (float)idx, start)
+                           : __builtin_fmaf(-step, (float)(steps - idx - 1), end);
+}
+
+// far - (far - near) / steps, the last position of the reference's equidistant samples, formed in
+// double and rounded once as the reference forms it (Python floats handed to torch.linspace).
+__device__ __forceinline__ float last_sample_start(float near_, float far_, int steps) {
+    return (float)((double)far_ - ((double)far_ - (double)near_) / (double)steps);
 }
 
 // ---------------------------------------------------------------------------

@@ -36,8 +36,9 @@ __global__ __launch_bounds__(256) void sample_uniform_kernel(int64_t n_rays, int
     const int64_t ray = idx / S;
     const int s = (int)(idx - ray * S);
     const float interval = (far_ - near_) / (float)S;
+    const float last = last_sample_start(near_, far_, S);
     auto t_at = [&](int ss) -> float {
-        float t = linspace_at(near_, far_ - interval, S, ss);
+        float t = linspace_at(near_, last, S, ss);
         if (stratified) t = t + philox_uniform(seed, counter, (uint64_t)(ray * S + ss)) * interval;
         if (offset_size != 0.0f) {
             // one uniform per ray, drawn from a disjoint counter stream
@@ -227,9 +228,10 @@ __global__ __launch_bounds__(256) void resample_finish_kernel(int64_t n_rays, in
     if (*status & 1) {
         // _sample_t_stratified_uniform(batch, n_samples, "equidistant", offset=-1)
         const float interval = (far_ - near_) / (float)N;
+        const float last = last_sample_start(near_, far_, N);
         const float u = philox_uniform(seed, counter ^ 0x8000000000000000ull, (uint64_t)ray);
         auto t_at = [&](int ss) -> float {
-            float t = linspace_at(near_, far_ - interval, N, ss);
+            float t = linspace_at(near_, last, N, ss);
             return t + (u * interval) * -1.0f;
         };
         t_start[idx] = t_at(s);

@@ -3,6 +3,10 @@ vectors and the CPU oracle.  Stated tolerances (fp32):
   encodings 2e-6 abs (same op order; ocml vs SLEEF sin/cos ulps),
   compositing 2e-6 abs on rgb / weights, 2e-5 on input gradients,
   resampling bit-exact, linear layers / field MLP 1e-4 (MFMA vs BLAS summation order).
+The compositing and sampling cases here are the common shapes.  The edge shapes of the stand-alone
+kernels (every R = ceil(S / 64) instantiation, S = 1, the walk past 8192 rays, each pointer layout,
+guard bands, the Philox draws and the fallback value for value, fewer than 64 bins) are in
+test_gpu_composite_edges.py and test_gpu_sampling_edges.py, against tests/_raypath_ref.py.
 """
 import math
 
