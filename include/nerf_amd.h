@@ -614,6 +614,34 @@ int nerf_linear_act_x3(int32_t kind, const nerf_seg* segs, int32_t n_segs, int64
                        float* grad_p1, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * SIREN's sine (nerf-siren/linear_sine.py:44-45, the activation of LinearSine; new entry points
+ * only, nerf_abi_version() stays 10).  Not an activation kind: nerf_param_act_* and
+ * nerf_linear_act_x3 keep refusing every kind but NERF_ACT_GABOR and NERF_ACT_SARF.
+ *   y = sin(z);  grad_z = grad_y * cos(z).
+ * sin / cos as the encodings compute them (within ~1e-7 absolute of the correctly rounded value
+ * for the |z| of a SIREN layer).  No learnable parameter: no column sums, no workspace.
+ * z, y, grad_y, grad_z are [M][N] row-major with their own row strides (>= N); grad_z may alias
+ * grad_y.  M == 0 or N == 0: NERF_OK, nothing launched.  A NULL pointer or a row stride below N:
+ * NERF_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------- */
+int nerf_sine_act_fwd(const float* z, int64_t ld_z, int64_t M, int32_t N, float* y, int64_t ld_y, void* stream);
+int nerf_sine_act_bwd(const float* grad_y, int64_t ld_g, const float* z, int64_t ld_z, int64_t M, int32_t N,
+                      float* grad_z, int64_t ld_dz, void* stream);
+
+/* Split-precision linear layer with the sine in its epilogue: nerf_linear_act_x3 without
+ * parameters, every element as nerf_sine_act_fwd / _bwd computes it.
+ *   mode NERF_GAUSS_FWD: z = A W^T + bias -> out, y = sin(z) -> y (row stride ld_y).
+ *   mode NERF_GAUSS_BWD: g = A W^T (bias must be NULL), z = this layer's pre-activation (row
+ *     stride ld_z); out = g * cos(z).
+ * Layers wider than 256 outputs run as column blocks of <= 256, in both modes: the sine's
+ * backward epilogue also runs on the 256-column tile (it forms no column sums).  Requires
+ * N % 4 == 0 and 16-byte aligned out / y / z / bias rows (row strides multiples of 4); returns
+ * NERF_ERR_UNSUPPORTED otherwise (callers then use nerf_linear_fwd_x3 + nerf_sine_act_fwd / _bwd). */
+int nerf_linear_sine_x3(const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw, int32_t N,
+                        const float* bias, float* out, int64_t ldo, int32_t mode, float* y, int64_t ld_y,
+                        const float* z, int64_t ld_z, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fused Adam step (the optimizer of every reference experiment: torch.optim.Adam(eps=1e-5),
  * barf/model_interpolation.py:543-584) for up to NERF_ADAM_MAX_TENSORS tensors in ONE launch.
  * Per element, in torch's fp32 operation order:

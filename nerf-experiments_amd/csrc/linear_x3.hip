@@ -184,6 +184,10 @@ __device__ __forceinline__ void gauss_bwd_store(float* o, f4 g, f4 z, f4 v, doub
 // stand-alone kernels, quad loads and stores as the Gaussian ones above.
 template <int ACT> struct ActSel { typedef GaborFn Fn; };
 template <> struct ActSel<NERF_ACT_SARF> { typedef SarfFn Fn; };
+// SIREN's sine (nerf_linear_sine_x3): an ACT value of the template only, refused as a `kind` by
+// every public entry point.  No parameters: its argument struct's gs / gs1 / part / part1 stay unused.
+constexpr int kActSine = SineFn::kKind;
+template <> struct ActSel<kActSine> { typedef SineFn Fn; };
 
 template <class Fn>
 __device__ __forceinline__ void act_fwd_store(float* o, float* yo, f4 z, const typename Fn::P (&k)[4]) {
@@ -447,7 +451,8 @@ typedef __attribute__((address_space(1))) void glb_void_t;
 __device__ __forceinline__ int swz128(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
 
 // ACT: 0 = the Gaussian activation for the NERF_EPI_GAUSS / _GAUSS_BWD epilogues, NERF_ACT_GABOR /
-// NERF_ACT_SARF = that activation in their place (compile-time: no branch in the epilogue loop).
+// NERF_ACT_SARF = that activation in their place (compile-time: no branch in the epilogue loop);
+// kActSine = SIREN's sine, which has no column partials to form.
 template <int EPI, int JN, int ACT = 0>
 __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTArgsSel<ACT>::T a, int ntiles) {
     constexpr int BM = 256, BN = 128 * JN;
@@ -739,7 +744,7 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTAr
                 pass(32 * p, p >> 2, acc[p & 3], acc[p & 3]);
             }
         }
-        if (GB) {
+        if constexpr (GB && (ACT == 0 || ActFn::kParams > 0)) {
             // the tile's inverse-std gradient column partials: the RS row groups of each column
             // quad added in order through the free A stage, one fp64 row per 256-row tile
             double* R = reinterpret_cast<double*>(C0);
@@ -2109,7 +2114,8 @@ extern "C" size_t nerf_linear_act_workspace(int32_t kind, int64_t M, int32_t N) 
            nerf::gauss_reduce_scratch(N);
 }
 
-template <int ACT>
+// BWD256: the activation's backward epilogue also exists on the 256-column tile (the sine's)
+template <int ACT, bool BWD256 = false>
 static void launch_act_glds(int epi, int nb, dim3 g3, dim3 b3, hipStream_t st, const NTActArgs& b, int ntiles) {
 #define NERF_ACT_LAUNCH(E)                                                                                \
     do {                                                                                                 \
@@ -2118,7 +2124,8 @@ static void launch_act_glds(int epi, int nb, dim3 g3, dim3 b3, hipStream_t st, c
     } while (0)
     if (epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) NERF_ACT_LAUNCH(NERF_EPI_GAUSS | NERF_EPI_BIAS);
     else if (epi == NERF_EPI_GAUSS) NERF_ACT_LAUNCH(NERF_EPI_GAUSS);
-    // the backward exists for 128-column tiles only (nerf_linear_act_x3 refuses wider ones)
+    // Gabor / Sarf: the backward exists for 128-column tiles only (nerf_linear_act_x3 refuses wider ones)
+    else if constexpr (BWD256) NERF_ACT_LAUNCH(NERF_EPI_GAUSS_BWD);
     else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS_BWD, 1, ACT>), g3, b3, 0, st, b, ntiles);
 #undef NERF_ACT_LAUNCH
 }
@@ -2196,6 +2203,48 @@ extern "C" int nerf_linear_act_x3(int32_t kind, const nerf_seg* segs, int32_t n_
         const int rc = nerf::param_act_reduce(kind, part + (size_t)n0 * ntiles, (int64_t)plane, ntiles, nb, p0 + n0,
                                               grad_p0 + n0, two ? grad_p1 + n0 : nullptr, accumulate, scratch, st);
         if (rc != NERF_OK) return rc;
+    }
+    return NERF_OK;
+}
+
+// nerf_linear_act_x3 with SIREN's sine (SineFn): no parameters, so no partial planes, no reduce
+// and no workspace.  Unlike Gabor / Sarf its backward epilogue (one sincos and one multiply per
+// element, no fp64 column sums) also runs on the 256-column tile.
+extern "C" int nerf_linear_sine_x3(const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw,
+                                   int32_t N, const float* bias, float* out, int64_t ldo, int32_t mode, float* y,
+                                   int64_t ld_y, const float* z, int64_t ld_z, void* stream) {
+    NERF_REQUIRE(M >= 0 && M < (1ll << 31) && N >= 1 && (mode == NERF_GAUSS_FWD || mode == NERF_GAUSS_BWD));
+    NERF_REQUIRE(out != nullptr);
+    const bool fwd = mode == NERF_GAUSS_FWD;
+    if (fwd) NERF_REQUIRE(y != nullptr && ld_y >= N);
+    else NERF_REQUIRE(bias == nullptr && z != nullptr && ld_z >= N);
+    if (M == 0) return NERF_OK;
+    // whole 16-byte quads everywhere, or the caller takes the unfused path
+    if ((N % 4) != 0 || !aligned16(out) || (ldo % 4) != 0 || ldo < N || (bias && !aligned16(bias)) ||
+        (fwd && (!aligned16(y) || (ld_y % 4) != 0)) || (!fwd && (!aligned16(z) || (ld_z % 4) != 0)))
+        return NERF_ERR_UNSUPPORTED;
+    SegList L;
+    NERF_REQUIRE(build_segs(segs, n_segs, L));
+    NERF_REQUIRE(W_x && aligned16(W_x) && ldw == L.ktot && (ldw % BK) == 0);
+    const int epi = fwd ? (NERF_EPI_GAUSS | (bias ? NERF_EPI_BIAS : 0)) : NERF_EPI_GAUSS_BWD;
+    hipStream_t st = as_stream(stream);
+    // 256-row tiles; column blocks of <= 256 (one for N <= 256)
+    const int ntiles = (int)((M + 255) / 256);
+    NTActArgs a{{L, (int)M, reinterpret_cast<const __bf16*>(W_x), ldw, N, bias, out, ldo, epi, z, ld_z, 1,
+                 nullptr, y, ld_y, nullptr}, nullptr, nullptr};
+    int grid = cu_count_x3();
+    if (grid > ntiles) grid = ntiles;
+    const dim3 g3((unsigned)grid), b3(512);
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        NTActArgs b = a;
+        b.N = N - n0 < 256 ? N - n0 : 256;
+        b.Wx = a.Wx + (size_t)n0 * 2 * ldw;
+        b.bias = bias ? bias + n0 : nullptr;
+        b.out = out + n0;
+        if (fwd) b.y2 = y + n0;
+        else b.aux = z + n0;
+        launch_act_glds<kActSine, true>(epi, b.N, g3, b3, st, b, ntiles);
+        NERF_CHECK_LAUNCH();
     }
     return NERF_OK;
 }

@@ -22,6 +22,7 @@
 // single exp whose argument error is relative to y.  Gabor takes the exact product p z as
 // hi + lo (one FMA); Sarf forms t, q and f / q in fp64 and splits the quotient.  Everything else
 // is fp32 arithmetic in the order written above.
+//   Sine   nerf-siren/linear_sine.py:44-45  (the activation of LinearSine; no parameters)
 #pragma once
 #include "common.h"
 
@@ -102,6 +103,28 @@ struct SarfFn {
         const float sg = z > 0.0f ? 1.0f : (z < 0.0f ? -1.0f : 0.0f);
         a0 += (double)(g * (((-s) * e) * (1.0f / q + 2.0f / ((k.f * k.f) * q2))));
         return (g * (e * ((s * k.f) / q2 - c))) * ((2.0f * t) * sg);
+    }
+};
+
+// SIREN's sine (nerf-siren/linear_sine.py:44-45): y = sin(z), dz = g * cos(z), no learnable
+// parameter (no column sums, no partial planes).  z is a GEMM output, not an exact product, so
+// the argument carries no rounding error of its own to keep: plain sincos_enc.  kKind is an
+// internal template value of the tile GEMM; no public entry point takes it as a kind.
+struct SineFn {
+    static constexpr int kKind = 3;
+    static constexpr int kParams = 0;
+    struct P {};
+    static __device__ __forceinline__ P load(const float*, const float*, int) { return P{}; }
+    static __device__ __forceinline__ float fwd(float z, P) {
+        float s, c;
+        sincos_enc(z, &s, &c);
+        return s;
+    }
+    static __device__ __forceinline__ float bwd(float g, float z, P, double&, double&) {
+#pragma clang fp contract(off)
+        float s, c;
+        sincos_enc(z, &s, &c);
+        return g * c;
     }
 };
 

@@ -8,6 +8,9 @@
 // and parameter (plane p at partial + p * slabs * N); the slabs are then summed in a fixed order
 // (nerf::gauss_reduce for Gabor's s, whose final * (2 s) is the same chain rule as GARF's;
 // nerf::param_reduce_plain for spread / frequency).  Deterministic, no atomics.
+//
+// SIREN's sine (nerf_sine_act_fwd / _bwd, nerf-siren/linear_sine.py:44-45) uses the same mapping
+// with SineFn: no parameter, so no partials, no reduce and no workspace.
 #include "param_act.h"
 
 using namespace nerf;
@@ -61,6 +64,20 @@ __global__ __launch_bounds__(256) void param_act_bwd_kernel(const float* g, int6
             partial[p * plane + (int64_t)blockIdx.x * N + n] =
                 ((red[p][0][c] + red[p][1][c]) + red[p][2][c]) + red[p][3][c];
     }
+}
+
+// SIREN's sine backward: the same mapping, no column sums (SineFn has no parameters).
+// grad_z may alias grad_y, as above.
+__global__ __launch_bounds__(256) void sine_act_bwd_kernel(const float* g, int64_t ldg, const float* __restrict__ z,
+                                                           int64_t ldz, int64_t M, int N, float* dz, int64_t lddz,
+                                                           int64_t rows_per_block) {
+    const int n = blockIdx.y * kCols + (threadIdx.x & (kCols - 1));
+    if (n >= N) return;
+    const int64_t m0 = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t m1 = m0 + rows_per_block < M ? m0 + rows_per_block : M;
+    double unused0 = 0.0, unused1 = 0.0;
+    for (int64_t m = m0 + (threadIdx.x >> 6); m < m1; m += kRowGroups)
+        dz[m * lddz + n] = SineFn::bwd(g[m * ldg + n], z[m * ldz + n], SineFn::P{}, unused0, unused1);
 }
 
 // the two levels of gauss.hip's column reduction, finished without a factor
@@ -187,4 +204,33 @@ extern "C" int nerf_param_act_bwd(int32_t kind, const float* grad_y, int64_t ld_
     NERF_CHECK_LAUNCH();
     return nerf::param_act_reduce(kind, partial, plane, slabs, N, p0, grad_p0, grad_p1, accumulate,
                                   partial + n_params(kind) * plane, st);
+}
+
+// ---------------------------------------------------------------------------- SIREN's sine
+extern "C" int nerf_sine_act_fwd(const float* z, int64_t ld_z, int64_t M, int32_t N, float* y, int64_t ld_y,
+                                 void* stream) {
+    NERF_REQUIRE(M >= 0 && N >= 0);
+    if (M == 0 || N == 0) return NERF_OK;
+    NERF_REQUIRE(z && y && ld_z >= N && ld_y >= N);
+    const int64_t slabs = slabs_for(M);
+    const int64_t rows = (M + slabs - 1) / slabs;
+    dim3 grid((unsigned)slabs, (unsigned)((N + kCols - 1) / kCols));
+    hipLaunchKernelGGL(param_act_fwd_kernel<SineFn>, grid, dim3(256), 0, as_stream(stream), z, ld_z,
+                       (const float*)nullptr, (const float*)nullptr, M, N, y, ld_y, rows);
+    NERF_CHECK_LAUNCH();
+    return NERF_OK;
+}
+
+extern "C" int nerf_sine_act_bwd(const float* grad_y, int64_t ld_g, const float* z, int64_t ld_z, int64_t M,
+                                 int32_t N, float* grad_z, int64_t ld_dz, void* stream) {
+    NERF_REQUIRE(M >= 0 && N >= 0);
+    if (M == 0 || N == 0) return NERF_OK;
+    NERF_REQUIRE(grad_y && z && grad_z && ld_g >= N && ld_z >= N && ld_dz >= N);
+    const int64_t slabs = slabs_for(M);
+    const int64_t rows = (M + slabs - 1) / slabs;
+    dim3 grid((unsigned)slabs, (unsigned)((N + kCols - 1) / kCols));
+    hipLaunchKernelGGL(sine_act_bwd_kernel, grid, dim3(256), 0, as_stream(stream), grad_y, ld_g, z, ld_z, M, N,
+                       grad_z, ld_dz, rows);
+    NERF_CHECK_LAUNCH();
+    return NERF_OK;
 }

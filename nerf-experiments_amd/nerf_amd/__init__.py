@@ -11,6 +11,8 @@ from .model_garf import GaussAct, ProposalNetwork, RadianceNetwork  # noqa: F401
 from .model_gaborf import GaborAct  # noqa: F401
 from .model_sarf import SarfAct  # noqa: F401
 from .model_ingp import INGPEncoding, INGPTable, NaiveINGP, NerfModelINGP  # noqa: F401
+# the SIREN field network stays nerf_amd.model_siren.NerfModel (NerfModel above is the interpolation one)
+from .model_siren import LinearSine, NerfSiren  # noqa: F401
 from .model_2d import FourierFeatures2d, Nerf2d  # noqa: F401
 from .model_ingp2d import Gigapixel  # noqa: F401  (its INGPTable / INGPEncoding stay in model_ingp2d)
 from .optim import FusedAdam  # noqa: F401

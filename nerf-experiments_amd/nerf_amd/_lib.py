@@ -218,6 +218,10 @@ _SIGNATURES = {
     "nerf_linear_act_x3": (c_i32, [c_i32, ctypes.POINTER(NerfSeg), c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
                                    c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
                                    c_sz, c_vp]),
+    "nerf_sine_act_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "nerf_sine_act_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "nerf_linear_sine_x3": (c_i32, [ctypes.POINTER(NerfSeg), c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64,
+                                    c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "nerf_linear_fwd": (c_i32, [ctypes.POINTER(NerfSeg), c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64,
                                 c_i32, c_vp, c_i64, c_vp]),
     "nerf_linear_wgrad_workspace": (c_sz, [c_i64, c_i32, c_i32]),

@@ -446,6 +446,28 @@ def param_act_bwd(kind: int, grad_y: torch.Tensor, z: torch.Tensor, N: int, para
     _lib.check(st, "nerf_param_act_bwd")
 
 
+# ------------------------------------------------------------------ SIREN's sine (param_act.hip)
+def sine_act_fwd(z: torch.Tensor, N: int, y: torch.Tensor) -> None:
+    """y[:, :N] = sin(z[:, :N]) (nerf_sine_act_fwd)."""
+    end = TIMER.bracket("sine_act_fwd", 0.0, 8.0 * z.shape[0] * N, fn="param_act_fwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_sine_act_fwd(_ptr(z), z.stride(0), z.shape[0], N, _ptr(y), y.stride(0), _stream(z.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_sine_act_fwd")
+
+
+def sine_act_bwd(grad_y: torch.Tensor, z: torch.Tensor, N: int, grad_z: torch.Tensor) -> None:
+    """grad_z[:, :N] = grad_y[:, :N] * cos(z[:, :N]) (nerf_sine_act_bwd; grad_z may be grad_y)."""
+    end = TIMER.bracket("sine_act_bwd", 0.0, 12.0 * z.shape[0] * N, fn="sine_act_bwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_sine_act_bwd(_ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0), z.shape[0], N,
+                                       _ptr(grad_z), grad_z.stride(0), _stream(z.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_sine_act_bwd")
+
+
 # ----------------------------------------------------------------------------- linear layers
 def make_segs(segs: Sequence[tuple[torch.Tensor, int, int]]):
     """segs: (tensor, k, row_div) with k % 4 == 0 valid columns; the tensor's row
@@ -607,6 +629,31 @@ def linear_act_x3(kind: int, segs, M: int, Wx: torch.Tensor, ldw: int, N: int, o
     if st == _lib.NERF_ERR_UNSUPPORTED:
         return False
     _lib.check(st, "nerf_linear_act_x3")
+    return True
+
+
+def linear_sine_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.Tensor, *,
+                   bias: torch.Tensor | None = None, y: torch.Tensor | None = None, z: torch.Tensor | None = None,
+                   w_row_offset: int = 0) -> bool:
+    """linear_act_x3 for SIREN's sine (nerf_linear_sine_x3): forward (y given) out = z = x W^T + b,
+    y = sin(z); input gradient (z given) out = dL/dz = (the product, dL/dy) * cos(z).  Returns False
+    when the shapes need the unfused path (N % 4, alignment)."""
+    arr = make_segs(segs)
+    off = w_row_offset * ldw * 2 * 2
+    fwd = y is not None
+    nbytes = _segs_bytes(segs, M) + 4.0 * N * ldw + (8.0 * M * N if fwd else 12.0 * M * N)
+    end = TIMER.bracket("linear_sine_x3" if fwd else "linear_sine_bwd_x3", 2.0 * M * N * ldw, nbytes,
+                        fn="linear_nt_x3_glds_kernel", launches=(N + 255) // 256) \
+        if TIMER is not None else None
+    st = _lib.load().nerf_linear_sine_x3(arr, len(segs), M, Wx.data_ptr() + off, ldw, N, _ptr(bias), _ptr(out),
+                                         out.stride(0), _lib.NERF_GAUSS_FWD if fwd else _lib.NERF_GAUSS_BWD,
+                                         _ptr(y), y.stride(0) if fwd else 0, _ptr(z),
+                                         z.stride(0) if z is not None else 0, _stream(out.device))
+    if end is not None:
+        end.record()
+    if st == _lib.NERF_ERR_UNSUPPORTED:
+        return False
+    _lib.check(st, "nerf_linear_sine_x3")
     return True
 
 

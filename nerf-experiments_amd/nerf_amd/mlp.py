@@ -321,7 +321,7 @@ def split_layers(plan, M: int, dir_rd: int) -> frozenset:
     cols = {li for li, _ in plan.column_outputs}
     out = set()
     for l, lp in enumerate(plan.layers[:-1]):
-        if lp.N > 256 or l in plan.outputs or l in cols or lp.pact or lp.tanh:
+        if lp.N > 256 or l in plan.outputs or l in cols or lp.keeps_pre or lp.tanh:
             continue
         readers = [(c, si) for c, cl in enumerate(plan.layers) for si, s in enumerate(cl.sources)
                    if s.kind == "act" and s.layer == l]
@@ -426,7 +426,9 @@ class LayerPlan:
     (RadianceNetwork's ``z1[:, :128] + z2[:, :128]``, garf/model_radiance.py:92).
     ``act`` = (kind, parameters) of a Gabor / Sarf activation (gaborf/gabor.py, sarf/activation.py:
     ``_lib.NERF_ACT_GABOR`` with (inv_standard_deviation, spread), ``_lib.NERF_ACT_SARF`` with
-    (frequency,)); it takes the routes, precision handling and eligibility rules of ``gauss``."""
+    (frequency,)); it takes the routes, precision handling and eligibility rules of ``gauss``.
+    ``sine`` = SIREN's ``sin`` (nerf-siren/linear_sine.py:44-45): the routes and precision handling of
+    ``gauss`` again (pre-activation kept; GEMM epilogue or separate pass), without parameters."""
     module: nn.Linear
     sources: list[Source]
     relu: bool
@@ -435,6 +437,7 @@ class LayerPlan:
     residual: int = -1
     residual_cols: int = 0
     tanh: bool = False     # tanh in the epilogue (2d-reconstruction/model.py:48-56); backward reads the output
+    sine: bool = False     # sin after the layer; exclusive with relu, gauss, act and tanh
     N: int = 0
     out_ld: int = 0
     Kp: int = 0
@@ -449,21 +452,29 @@ class LayerPlan:
     def __post_init__(self):
         if self.gauss is not None and self.act is not None:
             raise ValueError("LayerPlan: gauss= and act= are exclusive")
+        if self.sine and (self.relu or self.gauss is not None or self.act is not None or self.tanh):
+            raise ValueError("LayerPlan: sine= is exclusive with relu, gauss=, act= and tanh")
         # the learnable parameters of this layer's activation (Gaussian, Gabor or Sarf) in
         # state-dict order; empty without one.  Such a layer keeps its pre-activation.
         self.pact: tuple[nn.Parameter, ...] = ((self.gauss,) if self.gauss is not None
                                                else tuple(self.act[1]) if self.act is not None else ())
+        # the layer's output is an activation of a stored pre-activation (the backward reads it)
+        self.keeps_pre: bool = bool(self.pact) or self.sine
 
     def act_fwd(self, z, out):
         """The activation as a separate pass: out = act(z)."""
-        if self.gauss is not None:
+        if self.sine:
+            K.sine_act_fwd(z, self.N, out)
+        elif self.gauss is not None:
             K.gauss_act_fwd(z, self.N, self.gauss, out)
         else:
             K.param_act_fwd(self.act[0], z, self.N, self.act[1], out)
 
     def act_bwd(self, g, z, dz, grads):
         """The activation's backward as a separate pass (dz may be g)."""
-        if self.gauss is not None:
+        if self.sine:
+            K.sine_act_bwd(g, z, self.N, dz)
+        elif self.gauss is not None:
             K.gauss_act_bwd(g, z, self.N, self.gauss, dz, grads[0])
         else:
             K.param_act_bwd(self.act[0], g, z, self.N, self.act[1], dz, grads)
@@ -471,6 +482,9 @@ class LayerPlan:
     def linear_act_x3(self, segs, M, Wx, ldw, N, out, **kw) -> bool:
         """A GEMM with this layer's activation (forward: y=) or its backward (z=, grads=) in the
         epilogue; False when the shapes need the separate pass."""
+        if self.sine:
+            kw.pop("grads", None)
+            return K.linear_sine_x3(segs, M, Wx, ldw, N, out, **kw)
         if self.gauss is not None:
             if "grads" in kw:
                 kw["grad_inv_std"] = kw.pop("grads")[0]
@@ -480,7 +494,8 @@ class LayerPlan:
     def bwd_epilogue_fits(self, n: int) -> bool:
         """An input-gradient GEMM of n output columns can take this layer's activation backward in
         its epilogue: more than 32 columns (the split-precision tile kernels), and for Gabor / Sarf
-        at most 128 (nerf_linear_act_x3 has no 256-column backward: it would spill registers)."""
+        at most 128 (nerf_linear_act_x3 has no 256-column backward: it would spill registers; the
+        sine's, which forms no column sums, fits the 256-column tile and runs at any width)."""
         return n > 32 and (self.act is None or n <= 128)
 
     def finalize(self, device):
@@ -680,8 +695,8 @@ class MLPFunction(torch.autograd.Function):
                 # Gaussian layers: the GEMM writes the pre-activation z (kept for the backward) and,
                 # in split precision, exp(-z^2 v) into the layer's output from the same epilogue;
                 # otherwise nerf_gauss_act_fwd applies the activation in a second pass
-                target = torch.empty_like(out) if lp.pact else out
-                if (GAUSS_EPILOGUE and lp.pact and is_split(prec) and lp.N > 32 and lp.residual < 0
+                target = torch.empty_like(out) if lp.keeps_pre else out
+                if (GAUSS_EPILOGUE and lp.keeps_pre and is_split(prec) and lp.N > 32 and lp.residual < 0
                         and not lp.relu and lp.linear_act_x3(segs, M, lp.Wpx, lp.Kp, lp.N, target, bias=lp.module.bias,
                                                              y=out)):
                     pre.append(target)
@@ -702,7 +717,7 @@ class MLPFunction(torch.autograd.Function):
                     target[:, :rc].copy_(acts[lp.residual][:, :rc])
                     epi |= NERF_EPI_ACCUM
                 lp.gemm(prec, segs, M, False, lp.N, lp.module.bias, target, epi, aux=mask)
-                if lp.pact:
+                if lp.keeps_pre:
                     lp.act_fwd(target, out)
                     if lp.out_ld > lp.N:
                         out[:, lp.N:].zero_()
@@ -743,7 +758,7 @@ class MLPFunction(torch.autograd.Function):
         L = len(plan.layers)
         acts = list(saved[2:2 + L])
         pre_it = iter(saved[2 + L:])
-        pre = [next(pre_it) if lp.pact else None for lp in plan.layers]
+        pre = [next(pre_it) if lp.keeps_pre else None for lp in plan.layers]
         dev = pos.device
         dY: list[torch.Tensor | None] = [None] * L
         owned = [True] * L       # False: dY[i] is autograd's incoming tensor (never written in place)
@@ -877,7 +892,7 @@ class MLPFunction(torch.autograd.Function):
             gs = None
             if gauss_done[li] is not None:
                 gs = gauss_done[li]          # dY[li] already is dL/dz (the consumer's epilogue)
-            elif lp.pact:
+            elif lp.keeps_pre:
                 # dY -> dZ through the activation (+ its parameters' gradients)
                 gs = [torch.empty_like(p) for p in lp.pact]
                 dz = dZ if owned[li] else torch.empty_like(dZ)
@@ -898,7 +913,8 @@ class MLPFunction(torch.autograd.Function):
             nrow = lp.N if (lp.N == 257 and WGRAD_ROW257) else N4
             # which segments are quad-split images (ctx.split: chosen by the forward)
             q = tuple(s.kind == "act" and s.layer in ctx.split for s in lp.sources)
-            merge = sink is not None and is_split(ctx.prec) and MERGE_PASSES and gs is None
+            # (a stashed pass returns no activation-parameter gradients: only layers without any merge)
+            merge = sink is not None and is_split(ctx.prec) and MERGE_PASSES and not gs
             prev = sink.stash.pop((id(plan), li), (None, None))[0] if merge else None
             if merge and prev is None and sink.remaining(w) >= 2:
                 # another pass of this field lands its contribution later in this backward: its
@@ -941,7 +957,7 @@ class MLPFunction(torch.autograd.Function):
                 if s.kind == "act":
                     j = s.layer
                     prod = plan.layers[j]
-                    if (GAUSS_EPILOGUE and prod.pact and plan.contributors[j] == 1 and dY[j] is None
+                    if (GAUSS_EPILOGUE and prod.keeps_pre and plan.contributors[j] == 1 and dY[j] is None
                             and not prod.relu and is_split(ctx.prec) and prod.bwd_epilogue_fits(s.k_valid)):
                         # sole consumer: dL/dz of the Gaussian layer straight from this GEMM's epilogue
                         dz = torch.empty(M, prod.out_ld, device=dev, dtype=torch.float32)

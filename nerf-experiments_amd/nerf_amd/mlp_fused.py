@@ -61,7 +61,7 @@ CAPTURE_PER_RAY = os.environ.get("NERF_FUSED_CAPTURE", "1") != "0"
 def _layer_shape(plan, idx):
     """(kbr, hbm sources, act source) of layer idx, or None if the kernel cannot run it."""
     lp = plan.layers[idx]
-    if lp.pact or lp.tanh or lp.residual >= 0:
+    if lp.keeps_pre or lp.tanh or lp.residual >= 0:
         return None
     acts = [s for s in lp.sources if s.kind == "act"]
     hbm = [s for s in lp.sources if s.kind != "act"]

@@ -334,10 +334,17 @@ class NerfModelINGP(NerfModel):
         return density, rgb
 
 
-class NaiveINGP(nn.Module):
+class CoarseFineRenderer(nn.Module):
+    """The coarse / fine renderer 3d-ingp and nerf-siren share (nerf-siren/model.py:38-280, the
+    statement of it this module is written from): stratified coarse t, positions at the sample t,
+    distances = t differences plus far - t_last, compositing without a density factor, a fine pass
+    of samples_per_ray_coarse + samples_per_ray_fine samples from the round / argmax allocation
+    (mode 1 of nerf_resample_pdf) or multinomial draws (mode 2).  A subclass creates ``model_coarse``
+    and ``model_fine`` (``model(pos, dir) -> (density, rgb)``) and its optimizer."""
+
     def __init__(self, near_sphere_normalized: float, far_sphere_normalized: float, samples_per_ray_fine: int,
-                 samples_per_ray_coarse: int, position_encoder, direction_encoder, n_hidden: int, hidden_dim: int,
-                 learning_rate: float = 1e-4, learning_rate_decay: float = 0.5, weight_decay: float = 0.0):
+                 samples_per_ray_coarse: int, learning_rate: float = 1e-4, learning_rate_decay: float = 0.5,
+                 weight_decay: float = 0.0):
         super().__init__()
         self.near_sphere_normalized = near_sphere_normalized
         self.far_sphere_normalized = far_sphere_normalized
@@ -346,8 +353,6 @@ class NaiveINGP(nn.Module):
         self.learning_rate = learning_rate
         self.learning_rate_decay = learning_rate_decay
         self.weight_decay = weight_decay
-        self.model_coarse = NerfModelINGP(n_hidden, hidden_dim, position_encoder, direction_encoder)
-        self.model_fine = NerfModelINGP(n_hidden, hidden_dim, position_encoder, direction_encoder)
         # bit 0: the fine allocation fell back to equidistant samples; bit 1: a multinomial row was
         # not a distribution (nerf_resample_pdf; device int32, read only if the caller wants it)
         self.last_resample_status: th.Tensor | None = None
@@ -439,11 +444,24 @@ class NaiveINGP(nn.Module):
         loss_fine = nn.functional.mse_loss(fine, ray_colors)
         return loss_coarse + loss_fine, {"loss_coarse": loss_coarse.detach(), "loss_fine": loss_fine.detach()}
 
-    def configure_optimizers(self):
+    def _adam(self, **kw):
+        """Adam over every parameter at learning_rate / weight_decay (FusedAdam when all are on the GPU)."""
         params = list(self.parameters())
         opt_cls = FusedAdam if all(p.is_cuda for p in params) else th.optim.Adam
-        optimizer = opt_cls(params, lr=self.learning_rate, betas=(0.9, 0.99), eps=1e-15,
-                            weight_decay=self.weight_decay)
+        return opt_cls(params, lr=self.learning_rate, weight_decay=self.weight_decay, **kw)
+
+
+class NaiveINGP(CoarseFineRenderer):
+    def __init__(self, near_sphere_normalized: float, far_sphere_normalized: float, samples_per_ray_fine: int,
+                 samples_per_ray_coarse: int, position_encoder, direction_encoder, n_hidden: int, hidden_dim: int,
+                 learning_rate: float = 1e-4, learning_rate_decay: float = 0.5, weight_decay: float = 0.0):
+        super().__init__(near_sphere_normalized, far_sphere_normalized, samples_per_ray_fine,
+                         samples_per_ray_coarse, learning_rate, learning_rate_decay, weight_decay)
+        self.model_coarse = NerfModelINGP(n_hidden, hidden_dim, position_encoder, direction_encoder)
+        self.model_fine = NerfModelINGP(n_hidden, hidden_dim, position_encoder, direction_encoder)
+
+    def configure_optimizers(self):
+        optimizer = self._adam(betas=(0.9, 0.99), eps=1e-15)
         # no scheduler: the reference's ExponentialLR(gamma=learning_rate_decay) is commented out
         # (3d-ingp/model.py:503-519), so its learning rate stays constant
         return {"optimizer": optimizer}
