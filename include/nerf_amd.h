@@ -874,6 +874,86 @@ int nerf_pose_rays_bwd(const float* rotation, int32_t n_images, const int64_t* i
                        const float* g_t, const int64_t* ray_order, const int64_t* image_start, float* g_rotation,
                        float* g_translation, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Occupancy-grid ray marching (empty-space skipping): nerfacc's OccGridEstimator.sampling for one
+ * grid level and cone_angle 0, restated from its published behaviour with a contract of our own
+ * (nerfacc is not vendored: parity unpinned).  Rays get a variable number of samples ("packed"
+ * samples, ray-major, ascending along each ray).
+ *
+ * Grid: aabb = host [xmin, ymin, zmin, xmax, ymax, zmax] (lo < hi per axis), resolution = host
+ * [rx, ry, rz] (1..4096 each, at most 2^31 cells), grid_bits = device uint32 words, bit (i & 31) of
+ * word i >> 5 set iff cell i = (cx * ry + cy) * rz + cz is occupied.
+ *
+ * The marching contract, every operation rounded to fp32 separately (no contraction), division
+ * correctly rounded, max(a, b) = a > b ? a : b and min(a, b) = a < b ? a : b as written below:
+ *   1. per axis a with d_a == 0: no bound if lo_a <= o_a < hi_a, otherwise the ray misses;
+ *   2. else inv = 1 / d_a, ta = (lo_a - o_a) * inv, tb = (hi_a - o_a) * inv,
+ *      mn = ta < tb ? ta : tb, mx = ta < tb ? tb : ta;
+ *   3. tn = -inf, tf = +inf, then per axis tn = mn > tn ? mn : tn, tf = mx < tf ? mx : tf;
+ *   4. t_min = near > tn ? near : tn, t_max = far < tf ? far : tf;
+ *   5. the ray has samples only if t_min < t_max;
+ *   6. stratified: t_min = t_min + U[ray] * dt, U = Philox(seed, counter) uniform of index ray;
+ *   7. n = min(ceilf((t_max - t_min) / dt), NERF_OCC_MAX_STEPS) (0 below 1); a larger quotient
+ *      sets bit 0 of *status (device int32, OR-ed, never cleared by the call);
+ *   8. step k < n: t0 = t_min + (float)k * dt, e1 = t_min + (float)(k + 1) * dt,
+ *      t1 = e1 < t_max ? e1 : t_max; dropped unless t0 < t1;
+ *   9. tm = (t0 + t1) * 0.5, p_a = o_a + tm * d_a;
+ *  10. c_a = floorf(((p_a - lo_a) / (hi_a - lo_a)) * (float)res_a);
+ *  11. kept iff 0 <= c_a < res_a for every axis and the cell's bit is set (the grid is read only
+ *      after that range test);
+ *  12. so consecutive kept steps of a ray abut bitwise: t_ends[i] == t_starts[i + 1].
+ *
+ * Two passes over a caller-owned workspace of nerf_occ_march_workspace(n_rays, mask_words) bytes
+ * (0 on bad arguments), 256-byte aligned, not zeroed by the caller.  mask_words (1..128) is the
+ * number of 64-step masks kept per ray; a ray with n > 64 * mask_words is cut there and sets bit 1
+ * of *status, so a caller that cannot bound its rays' steps passes 128 (NERF_OCC_MAX_STEPS / 64).
+ * nerf_occ_march_count stores per ray the kept count (int64, the first n_rays * 8 bytes of the
+ * workspace), t_min, t_max, n and one 64-bit mask per 64 steps.  The caller forms the inclusive
+ * prefix sum of the counts (offsets_incl [n_rays] int64; its last element is the sample total) and
+ * allocates the outputs.  nerf_occ_march_write places every kept step from the stored masks (slot =
+ * offset + popcount of the lower mask bits); it never tests the grid, and no store lands at or
+ * past n_samples.  One wave per ray; no allocation; the caller's stream.
+ * Status codes: a null or misaligned pointer with n_rays > 0, a bad grid, mask_words or step_size:
+ * NERF_ERR_INVALID_ARG; a short workspace: NERF_ERR_WORKSPACE; before any launch.  n_rays == 0 (and
+ * n_samples == 0 for the write) succeeds without a kernel.
+ * ------------------------------------------------------------------------- */
+#define NERF_OCC_MAX_STEPS 8192
+size_t nerf_occ_march_workspace(int64_t n_rays, int32_t mask_words);
+int nerf_occ_march_count(const float* rays_o, const float* rays_d, int64_t n_rays, const float* aabb,
+                         const int32_t* resolution, const uint32_t* grid_bits, float near_plane, float far_plane,
+                         float step_size, int32_t stratified, uint64_t seed, uint64_t counter, int32_t mask_words,
+                         void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+int nerf_occ_march_write(int64_t n_rays, float step_size, int32_t mask_words, const void* workspace,
+                         size_t workspace_bytes, const int64_t* offsets_incl, int64_t n_samples,
+                         int64_t* ray_indices, float* t_starts, float* t_ends, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Compositing of packed samples: ray r owns samples [seg[r], seg[r+1]) of the flat arrays (seg
+ * [n_rays + 1] int64, non-decreasing, clamped to [0, n_samples] by the kernels).  The arithmetic of
+ * nerf_composite_fwd with scale 1 and act 0 on segments of any length:
+ *   b_i = -sigma_i * (t_ends_i - t_starts_i), T_i = exp(fp64 sum of b over the ray's earlier
+ *   samples, rounded to fp32) (1 for the first), alpha_i = -expm1(b_i) (relative accuracy for the
+ *   thin samples of a marched ray), w_i = T_i * alpha_i;
+ *   colors = sum w c, opacity = sum w, depth = sum w (t_starts + t_ends) / 2; zeros for an empty ray.
+ * sigma (stride sigma_stride), rgb (row stride rgb_stride >= 3; NULL: weights only).  Outputs (each
+ * optional): colors [n_rays][3], opacity [n_rays], depth [n_rays], weights, trans, alphas [n_samples].
+ * nerf_composite_packed_bwd: gradients of <g_colors, colors> + <g_opacity, opacity> + <g_depth,
+ * depth> + <g_weights, weights> (each g optional, NULL = zero) to sigma (grad_sigma, stride
+ * gs_stride) and rgb (grad_rgb, row stride gc_stride), each optional; weights and trans are the
+ * forward's outputs.  One wave per ray, fp64 wave scans, no atomics: deterministic.
+ * n_rays == 0: NERF_OK without a launch; null or misaligned pointers: NERF_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------- */
+int nerf_composite_packed_fwd(const float* sigma, int64_t sigma_stride, const float* rgb, int64_t rgb_stride,
+                              const float* t_starts, const float* t_ends, const int64_t* seg, int64_t n_rays,
+                              int64_t n_samples, float* colors, float* opacity, float* depth, float* weights,
+                              float* trans, float* alphas, void* stream);
+int nerf_composite_packed_bwd(const float* sigma, int64_t sigma_stride, const float* rgb, int64_t rgb_stride,
+                              const float* t_starts, const float* t_ends, const int64_t* seg, int64_t n_rays,
+                              int64_t n_samples, const float* weights, const float* trans, const float* g_colors,
+                              const float* g_opacity, const float* g_depth, const float* g_weights,
+                              float* grad_sigma, int64_t gs_stride, float* grad_rgb, int64_t gc_stride,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

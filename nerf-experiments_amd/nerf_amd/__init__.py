@@ -17,6 +17,7 @@ from .model_2d import FourierFeatures2d, Nerf2d  # noqa: F401
 from .model_ingp2d import Gigapixel  # noqa: F401  (its INGPTable / INGPEncoding stay in model_ingp2d)
 from .optim import FusedAdam  # noqa: F401
 from .pose import compute_pose_error, kabsch_algorithm, validation_transform_rays  # noqa: F401
-from .prop_sampler import PropNetEstimator, rendering  # noqa: F401
+from .prop_sampler import PropNetEstimator, render_weight_from_density, rendering  # noqa: F401
+from .occ_grid import OccGridEstimator  # noqa: F401
 
 __version__ = "0.1.0"

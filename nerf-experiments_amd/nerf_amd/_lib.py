@@ -46,6 +46,7 @@ def NERF_FUSED_SPLIT_OUT(layer: int) -> int:
 
 NERF_KABSCH_MAX_POINTS = 4096
 NERF_PROP_MAX_EDGES = 512
+NERF_OCC_MAX_STEPS = 8192
 NERF_GAUSS_FWD = 0
 NERF_GAUSS_BWD = 1
 NERF_ACT_GABOR = 1
@@ -279,6 +280,14 @@ _SIGNATURES = {
     "nerf_hashgrid2d_workspace": (c_sz, [ctypes.POINTER(NerfHashgridParams)]),
     "nerf_hashgrid2d_bwd": (c_i32, [ctypes.POINTER(NerfHashgridParams), c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp,
                                     c_sz, c_vp]),
+    "nerf_occ_march_workspace": (c_sz, [c_i64, c_i32]),
+    "nerf_occ_march_count": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_f), ctypes.POINTER(c_i32), c_vp, c_f, c_f,
+                                     c_f, c_i32, c_u64, c_u64, c_i32, c_vp, c_sz, c_vp, c_vp]),
+    "nerf_occ_march_write": (c_i32, [c_i64, c_f, c_i32, c_vp, c_sz, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "nerf_composite_packed_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp]),
+    "nerf_composite_packed_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

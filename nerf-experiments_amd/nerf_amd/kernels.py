@@ -1220,3 +1220,124 @@ def prop_loss(q_vals, q_cdf, k_vals, k_cdf, eps: float, grad_scale: float = 0.0,
                                           float(grad_scale), _ptr(gw), gw.stride(0) if gw is not None else 0,
                                           _stream(q_vals.device)), "nerf_prop_loss")
     return lr, gw
+
+
+# ----------------------------------------------------------------------------- occupancy-grid marching
+def occ_mask_words(near: float, far: float, step_size: float) -> int:
+    """64-step masks per ray that no ray of [near, far] at this step size can exceed: t_max - t_min <=
+    far - near whatever the direction, plus two steps for the fp32 rounding of the kernel's quotient."""
+    span = (float(far) - float(near)) / float(step_size)
+    if not span < _lib.NERF_OCC_MAX_STEPS:       # also NaN / inf
+        return _lib.NERF_OCC_MAX_STEPS // 64
+    return min(_lib.NERF_OCC_MAX_STEPS // 64, max(1, (int(span) + 3 + 63) // 64))
+
+
+def occ_march_workspace_bytes(n_rays: int, mask_words: int) -> int:
+    return int(_lib.load().nerf_occ_march_workspace(n_rays, mask_words))
+
+
+def occ_march_count(rays_o: torch.Tensor, rays_d: torch.Tensor, aabb: Sequence[float], resolution: Sequence[int],
+                    grid_bits: torch.Tensor, near: float, far: float, step_size: float, stratified: bool, seed: int,
+                    mask_words: int, workspace: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """Pass 1 of the marching (nerf_occ_march_count): fills `workspace` and returns the per-ray kept
+    counts, an int64 [n_rays] view of its first bytes."""
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        _require_cuda_f32(name, t)
+        if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [n_rays, 3] tensor")
+    if rays_d.shape != rays_o.shape:
+        raise ValueError("rays_o and rays_d must share their shape")
+    if grid_bits.dtype != torch.int32 or not grid_bits.is_contiguous() or grid_bits.device != rays_o.device:
+        raise ValueError("grid_bits must be a contiguous int32 tensor on the rays' device")
+    cells = int(resolution[0]) * int(resolution[1]) * int(resolution[2])
+    if grid_bits.numel() * 32 < cells:
+        raise ValueError(f"grid_bits holds {grid_bits.numel() * 32} bits for {cells} cells")
+    n = rays_o.shape[0]
+    box = (_lib.c_f * 6)(*[float(v) for v in aabb])
+    res = (_lib.c_i32 * 3)(*[int(v) for v in resolution])
+    st = _lib.load().nerf_occ_march_count(_ptr(rays_o), _ptr(rays_d), n, box, res, _ptr(grid_bits), float(near),
+                                          float(far), float(step_size), int(stratified), seed, 0, mask_words,
+                                          _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                          _ptr(status), _stream(rays_o.device))
+    _lib.check(st, "nerf_occ_march_count")
+    return workspace.view(torch.uint8)[:8 * n].view(torch.int64)
+
+
+def occ_march_write(n_rays: int, step_size: float, mask_words: int, workspace: torch.Tensor, offsets_incl: torch.Tensor,
+                    n_samples: int):
+    """Pass 2 (nerf_occ_march_write): (ray_indices int64 [N], t_starts [N], t_ends [N]) from the masks
+    pass 1 stored; offsets_incl is the inclusive prefix sum of pass 1's counts."""
+    if offsets_incl.dtype != torch.int64 or not offsets_incl.is_contiguous() or offsets_incl.numel() != n_rays:
+        raise ValueError("offsets_incl must be a contiguous int64 [n_rays] tensor")
+    dev = workspace.device
+    ray_indices = torch.empty(n_samples, device=dev, dtype=torch.int64)
+    t_starts = torch.empty(n_samples, device=dev, dtype=torch.float32)
+    t_ends = torch.empty(n_samples, device=dev, dtype=torch.float32)
+    st = _lib.load().nerf_occ_march_write(n_rays, float(step_size), mask_words, _ptr(workspace),
+                                          workspace.numel() * workspace.element_size(), _ptr(offsets_incl),
+                                          n_samples, _ptr(ray_indices), _ptr(t_starts), _ptr(t_ends), _stream(dev))
+    _lib.check(st, "nerf_occ_march_write")
+    return ray_indices, t_starts, t_ends
+
+
+# ----------------------------------------------------------------------------- packed compositing
+def _packed_inputs(sigma, rgb, t_starts, t_ends, seg):
+    for name, t in (("sigma", sigma), ("t_starts", t_starts), ("t_ends", t_ends)):
+        _require_cuda_f32(name, t)
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [n_samples] tensor")
+    n = sigma.shape[0]
+    if t_starts.shape[0] != n or t_ends.shape[0] != n:
+        raise ValueError("sigma, t_starts and t_ends must have one entry per sample")
+    if rgb is not None:
+        _require_cuda_f32("rgb", rgb)
+        if tuple(rgb.shape) != (n, 3) or not rgb.is_contiguous():
+            raise ValueError("rgb must be a contiguous [n_samples, 3] tensor")
+    if seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1 or not seg.is_contiguous() \
+            or seg.device != sigma.device:
+        raise ValueError("seg must be a contiguous int64 [n_rays + 1] tensor on the samples' device")
+    return seg.numel() - 1, n
+
+
+def composite_packed_fwd(sigma: torch.Tensor, rgb: torch.Tensor | None, t_starts: torch.Tensor, t_ends: torch.Tensor,
+                         seg: torch.Tensor):
+    """nerf_composite_packed_fwd: (colors [R, 3] or None without rgb, opacity [R], depth [R], weights [N],
+    trans [N], alphas [N]) of the rays owning samples [seg[r], seg[r+1])."""
+    R, n = _packed_inputs(sigma, rgb, t_starts, t_ends, seg)
+    f = dict(device=sigma.device, dtype=torch.float32)
+    colors = torch.empty(R, 3, **f) if rgb is not None else None
+    opacity, depth = torch.empty(R, **f), torch.empty(R, **f)
+    weights, trans, alphas = torch.empty(n, **f), torch.empty(n, **f), torch.empty(n, **f)
+    # algorithmic bytes: sigma, t_starts, t_ends (+ rgb) in, weights, trans, alphas out per sample
+    end = TIMER.bracket("composite_packed_fwd", nbytes=n * (24 + (12 if rgb is not None else 0)) + 28 * R,
+                        fn="composite_packed_fwd_kernel") if TIMER is not None else None
+    st = _lib.load().nerf_composite_packed_fwd(_ptr(sigma), 1, _ptr(rgb), 3, _ptr(t_starts), _ptr(t_ends), _ptr(seg),
+                                               R, n, _ptr(colors), _ptr(opacity), _ptr(depth), _ptr(weights),
+                                               _ptr(trans), _ptr(alphas), _stream(sigma.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_composite_packed_fwd")
+    return colors, opacity, depth, weights, trans, alphas
+
+
+def composite_packed_bwd(sigma, rgb, t_starts, t_ends, seg, weights, trans, g_colors, g_opacity, g_depth, g_weights,
+                         want_sigma: bool = True, want_rgb: bool = True):
+    """nerf_composite_packed_bwd: (d sigma [N] or None, d rgb [N, 3] or None); each g may be None (zero)."""
+    R, n = _packed_inputs(sigma, rgb, t_starts, t_ends, seg)
+    gs = [None if g is None else g.contiguous() for g in (g_colors, g_opacity, g_depth, g_weights)]
+    for g, numel in zip(gs, (3 * R, R, R, n)):
+        if g is not None and (g.dtype != torch.float32 or g.numel() != numel or g.device != sigma.device):
+            raise ValueError("output gradients must be float32 tensors of their outputs' sizes")
+    want_rgb = want_rgb and rgb is not None
+    d_sigma = torch.empty_like(sigma) if want_sigma else None
+    d_rgb = torch.empty_like(rgb) if want_rgb else None
+    end = TIMER.bracket("composite_packed_bwd", nbytes=n * (24 + (12 if rgb is not None else 0) + (4 if want_sigma else 0)
+                                                            + (12 if want_rgb else 0)) + 20 * R,
+                        fn="composite_packed_bwd_kernel") if TIMER is not None else None
+    st = _lib.load().nerf_composite_packed_bwd(_ptr(sigma), 1, _ptr(rgb), 3, _ptr(t_starts), _ptr(t_ends), _ptr(seg),
+                                               R, n, _ptr(weights), _ptr(trans), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]),
+                                               _ptr(gs[3]), _ptr(d_sigma), 1, _ptr(d_rgb), 3, _stream(sigma.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_composite_packed_bwd")
+    return d_sigma, d_rgb

@@ -18,7 +18,9 @@ restatement of the same algorithm):
     interval (w from the radiance pass's trans, detached; w_outer the proposal's cdf mass over
     the key intervals overlapping it), averaged, summed over proposal levels.
 Kernels: nerf_prop_sample / nerf_prop_cdf / nerf_prop_loss (csrc/propnet.hip); compositing is
-nerf_composite_fwd/bwd with density factor 1.
+nerf_composite_fwd/bwd with density factor 1 for batched samples and nerf_composite_packed_fwd/bwd
+(csrc/composite_packed.hip) for packed ones (``ray_indices``, the output of
+``nerf_amd.occ_grid.OccGridEstimator.sampling``).
 """
 from __future__ import annotations
 
@@ -109,16 +111,91 @@ class PropNetEstimator:
         return loss * loss_scaler
 
 
+class _PackedRenderFn(th.autograd.Function):
+    """nerf_composite_packed_fwd / _bwd on flat samples: (colors or None, opacity, depth, weights, trans,
+    alphas); one node carries the gradients of colors, opacity, depth and weights to sigmas and rgbs."""
+
+    @staticmethod
+    def forward(ctx, sigmas, rgbs, t_starts, t_ends, seg):
+        sigmas, t_starts, t_ends = sigmas.contiguous(), t_starts.contiguous(), t_ends.contiguous()
+        rgbs = rgbs.contiguous() if rgbs is not None else None
+        colors, opacity, depth, weights, trans, alphas = K.composite_packed_fwd(sigmas, rgbs, t_starts, t_ends, seg)
+        ctx.has_rgb = rgbs is not None
+        ctx.save_for_backward(sigmas, t_starts, t_ends, seg, weights, trans, *(() if rgbs is None else (rgbs,)))
+        ctx.mark_non_differentiable(trans, alphas)
+        if colors is None:
+            colors = sigmas.new_zeros(0)
+            ctx.mark_non_differentiable(colors)
+        return colors, opacity, depth, weights, trans, alphas
+
+    @staticmethod
+    def backward(ctx, g_colors, g_opacity, g_depth, g_weights, _g_trans, _g_alphas):
+        sigmas, t_starts, t_ends, seg, weights, trans, *rest = ctx.saved_tensors
+        rgbs = rest[0] if ctx.has_rgb else None
+        d_sigma, d_rgb = K.composite_packed_bwd(sigmas, rgbs, t_starts, t_ends, seg, weights, trans,
+                                                g_colors if ctx.has_rgb else None, g_opacity, g_depth, g_weights,
+                                                want_sigma=ctx.needs_input_grad[0],
+                                                want_rgb=ctx.has_rgb and ctx.needs_input_grad[1])
+        return d_sigma, d_rgb, None, None, None
+
+
+def _segments(ray_indices: th.Tensor, n_rays: int) -> th.Tensor:
+    """seg [n_rays + 1]: ray r owns samples [seg[r], seg[r+1]) of ray_indices sorted ascending (the
+    contract, nerfacc's too; not checked, that would take a synchronisation)."""
+    if ray_indices.dtype != th.int64 or ray_indices.dim() != 1:
+        raise ValueError("ray_indices must be an int64 [n_samples] tensor")
+    return th.searchsorted(ray_indices.contiguous(), th.arange(n_rays + 1, device=ray_indices.device))
+
+
+def render_weight_from_density(t_starts: th.Tensor, t_ends: th.Tensor, sigmas: th.Tensor,
+                               ray_indices: Optional[th.Tensor] = None, n_rays: Optional[int] = None):
+    """nerfacc.render_weight_from_density: (weights, trans, alphas), shaped like sigmas.  Packed
+    samples: flat [N] tensors with ray_indices (sorted ascending) and n_rays; batched [R, S] tensors
+    with ray_indices=None run the same kernel on equal segments.  Differentiable in sigmas."""
+    if ray_indices is None:
+        if sigmas.dim() != 2:
+            raise ValueError("without ray_indices, t_starts / t_ends / sigmas must be [n_rays, n_samples]")
+        R, S = sigmas.shape
+        seg = th.arange(R + 1, device=sigmas.device) * S
+    else:
+        if n_rays is None:
+            raise ValueError("n_rays is required with ray_indices (reading it off the device would synchronise)")
+        seg = _segments(ray_indices, n_rays)
+    shape = sigmas.shape
+    _, _, _, weights, trans, alphas = _PackedRenderFn.apply(sigmas.reshape(-1), None, t_starts.reshape(-1),
+                                                            t_ends.reshape(-1), seg)
+    return weights.view(shape), trans.view(shape), alphas.view(shape)
+
+
+def _rendering_packed(t_starts, t_ends, ray_indices, n_rays, rgb_sigma_fn, render_bkgd):
+    if n_rays is None:
+        raise ValueError("n_rays is required with ray_indices (reading it off the device would synchronise)")
+    if t_starts.dim() != 1 or t_ends.shape != t_starts.shape or ray_indices.shape != t_starts.shape:
+        raise ValueError("with ray_indices, t_starts / t_ends / ray_indices must be flat [n_samples] tensors")
+    rgbs, sigmas = rgb_sigma_fn(t_starts, t_ends, ray_indices)
+    N = t_starts.shape[0]
+    colors, opacity, depth, weights, trans, alphas = _PackedRenderFn.apply(
+        sigmas.reshape(N), rgbs.reshape(N, 3), t_starts, t_ends, _segments(ray_indices, n_rays))
+    opacities, depths = opacity.unsqueeze(-1), depth.unsqueeze(-1)
+    if render_bkgd is not None:
+        colors = colors + render_bkgd * (1.0 - opacities)
+    return colors, opacities, depths, {"weights": weights, "trans": trans, "sigmas": sigmas, "rgbs": rgbs,
+                                       "alphas": alphas}
+
+
 def rendering(t_starts: th.Tensor, t_ends: th.Tensor, ray_indices: Optional[th.Tensor] = None,
               n_rays: Optional[int] = None, rgb_sigma_fn: Optional[Callable] = None,
               render_bkgd: Optional[th.Tensor] = None):
-    """nerfacc.rendering for batched [n_rays, n_samples] intervals (ray_indices must be None):
-    (colors [R, 3], opacities [R, 1], depths [R, 1], extras) with extras weights / trans / sigmas /
-    rgbs / alphas; trans (exclusive transmittance, 1 - the exclusive weight sum) is detached."""
-    if ray_indices is not None:
-        raise NotImplementedError("nerf_amd.prop_sampler.rendering supports batched (ray_indices=None) samples")
+    """nerfacc.rendering: (colors [R, 3], opacities [R, 1], depths [R, 1], extras) with extras weights /
+    trans / sigmas / rgbs / alphas; trans (exclusive transmittance) is detached.
+    ray_indices=None: batched [n_rays, n_samples] intervals (nerf_composite_fwd / _bwd).
+    ray_indices given: packed samples, flat [N] tensors with ray_indices int64 sorted ascending and
+    n_rays stated (nerf_composite_packed_fwd / _bwd); rgb_sigma_fn receives (t_starts, t_ends,
+    ray_indices), the per-sample extras are flat, and a ray without samples renders zeros."""
     if rgb_sigma_fn is None:
         raise ValueError("rgb_sigma_fn is required")
+    if ray_indices is not None:
+        return _rendering_packed(t_starts, t_ends, ray_indices, n_rays, rgb_sigma_fn, render_bkgd)
     rgbs, sigmas = rgb_sigma_fn(t_starts, t_ends, None)
     R, S = t_starts.shape
     delta = (t_ends - t_starts).contiguous()
@@ -134,4 +211,4 @@ def rendering(t_starts: th.Tensor, t_ends: th.Tensor, ray_indices: Optional[th.T
                                        "alphas": alphas}
 
 
-__all__ = ["PropNetEstimator", "rendering"]
+__all__ = ["PropNetEstimator", "rendering", "render_weight_from_density"]
