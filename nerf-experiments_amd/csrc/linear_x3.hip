@@ -143,51 +143,25 @@ struct NTActArgs : NTArgs {
 template <int ACT> struct NTArgsSel { typedef NTActArgs T; };
 template <> struct NTArgsSel<0> { typedef NTArgs T; };
 
-// Gaussian activation (garf/gaussian.py:8-31) on a column quad, with exactly the element
-// formulas of gauss.hip: v = s^2 + 1e-6, y = exp((-(z*z)) * v); backward ge = g * exp((-(z*z)) v),
-// dz = (((-ge) * 2) * z) * v, column partial += (double)((-ge) * z^2).
-__device__ __forceinline__ f4 gauss_v4(const float* s, int n) {
-#pragma clang fp contract(off)
-    const f4 sv = *reinterpret_cast<const f4*>(s + n);
-    return sv * sv + 1e-6f;
-}
-
-__device__ __forceinline__ void gauss_fwd_store(float* o, float* yo, f4 z, f4 v) {
-#pragma clang fp contract(off)
-    __builtin_nontemporal_store(z, reinterpret_cast<f4*>(o));
-    f4 y;
-    y.x = expf((-(z.x * z.x)) * v.x);
-    y.y = expf((-(z.y * z.y)) * v.y);
-    y.z = expf((-(z.z * z.z)) * v.z);
-    y.w = expf((-(z.w * z.w)) * v.w);
-    __builtin_nontemporal_store(y, reinterpret_cast<f4*>(yo));
-}
-
-__device__ __forceinline__ float gauss_bwd1(float g, float zz, float v, double& acc) {
-#pragma clang fp contract(off)
-    const float z2 = zz * zz;
-    const float ge = g * expf((-z2) * v);
-    acc += (double)((-ge) * z2);
-    return (((-ge) * 2.0f) * zz) * v;
-}
-
-__device__ __forceinline__ void gauss_bwd_store(float* o, f4 g, f4 z, f4 v, double (&acc)[4]) {
-    f4 dz;
-    dz.x = gauss_bwd1(g.x, z.x, v.x, acc[0]);
-    dz.y = gauss_bwd1(g.y, z.y, v.y, acc[1]);
-    dz.z = gauss_bwd1(g.z, z.z, v.z, acc[2]);
-    dz.w = gauss_bwd1(g.w, z.w, v.w, acc[3]);
-    __builtin_nontemporal_store(dz, reinterpret_cast<f4*>(o));
-}
-
-// Gabor / Sarf activations (param_act.h) on a column quad: the element functions of the
-// stand-alone kernels, quad loads and stores as the Gaussian ones above.
-template <int ACT> struct ActSel { typedef GaborFn Fn; };
+// The activations (param_act.h) on a column quad: the element functions of the stand-alone
+// kernels, quad loads and stores.  ACT 0 = GARF's Gaussian (the NTArgs kernels' own), NERF_ACT_GABOR /
+// NERF_ACT_SARF, and SIREN's sine (nerf_linear_sine_x3): an ACT value of the template only, refused
+// as a `kind` by every public entry point; no parameters, so its gs / gs1 / part / part1 stay unused.
+template <int ACT> struct ActSel { typedef GaussFn Fn; };
+template <> struct ActSel<NERF_ACT_GABOR> { typedef GaborFn Fn; };
 template <> struct ActSel<NERF_ACT_SARF> { typedef SarfFn Fn; };
-// SIREN's sine (nerf_linear_sine_x3): an ACT value of the template only, refused as a `kind` by
-// every public entry point.  No parameters: its argument struct's gs / gs1 / part / part1 stay unused.
 constexpr int kActSine = SineFn::kKind;
 template <> struct ActSel<kActSine> { typedef SineFn Fn; };
+
+// the second parameter, which only NTActArgs carries
+__device__ __forceinline__ const float* second_param(const NTArgs&) { return nullptr; }
+__device__ __forceinline__ const float* second_param(const NTActArgs& a) { return a.gs1; }
+
+template <class Fn, class Args>
+__device__ __forceinline__ void act_load4(const Args& a, int n, typename Fn::P (&k)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) k[e] = Fn::load(a.gs, second_param(a), n + e);
+}
 
 template <class Fn>
 __device__ __forceinline__ void act_fwd_store(float* o, float* yo, f4 z, const typename Fn::P (&k)[4]) {
@@ -392,14 +366,15 @@ __global__ __launch_bounds__(256, 2) void linear_nt_x3_kernel(NTArgs a, int ntm,
                 if (gmode) {
                     // N % 4 == 0 and 16-byte rows (nerf_linear_gauss_x3 checks): whole quads
                     if (m < a.M && n < a.N) {
-                        const f4 v = gauss_v4(a.gs, n);
+                        GaussFn::P k[4];
+                        act_load4<GaussFn>(a, n, k);
                         if (a.epi & NERF_EPI_GAUSS) {
                             f4 z = c;
                             if (a.epi & NERF_EPI_BIAS) z += *reinterpret_cast<const f4*>(a.bias + n);
-                            gauss_fwd_store(a.out + (int64_t)m * a.ldo + n, a.y2 + (int64_t)m * a.ldy2 + n, z, v);
+                            act_fwd_store<GaussFn>(a.out + (int64_t)m * a.ldo + n, a.y2 + (int64_t)m * a.ldy2 + n, z, k);
                         } else {
-                            gauss_bwd_store(a.out + (int64_t)m * a.ldo + n, c,
-                                            *reinterpret_cast<const f4*>(a.aux + (int64_t)m * a.ldaux + n), v, gp);
+                            act_bwd_store<GaussFn>(a.out + (int64_t)m * a.ldo + n, c,
+                                                   *reinterpret_cast<const f4*>(a.aux + (int64_t)m * a.ldaux + n), k, gp, gp);   // (no second parameter)
                         }
                     }
                 } else {
@@ -614,18 +589,11 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTAr
     f4 bias4 = f4{0.f, 0.f, 0.f, 0.f};
     if ((EPI & NERF_EPI_BIAS) && a.vec_ok && en + 4 <= a.N) bias4 = *reinterpret_cast<const f4*>(a.bias + en);
     constexpr bool GF = (EPI & NERF_EPI_GAUSS) != 0, GB = (EPI & NERF_EPI_GAUSS_BWD) != 0;
-    f4 gv4 = f4{0.f, 0.f, 0.f, 0.f};
-    if (ACT == 0 && (GF || GB) && en + 4 <= a.N) gv4 = gauss_v4(a.gs, en);
     double gp[4] = {0.0, 0.0, 0.0, 0.0};          // GB: this thread's column-quad partials of the tile
     typedef typename ActSel<ACT>::Fn ActFn;
-    typename ActFn::P kp[4] = {};                 // ACT != 0: the quad's activation parameters
-    double gq[4] = {0.0, 0.0, 0.0, 0.0};          // ACT != 0, GB: partials of the second parameter
-    if constexpr (ACT != 0) {
-        if ((GF || GB) && en + 4 <= a.N) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) kp[e] = ActFn::load(a.gs, a.gs1, en + e);
-        }
-    }
+    typename ActFn::P kp[4] = {};                 // GF / GB: the quad's activation parameters
+    double gq[4] = {0.0, 0.0, 0.0, 0.0};          // GB: partials of the second parameter
+    if ((GF || GB) && en + 4 <= a.N) act_load4<ActFn>(a, en, kp);
     const EpiOut E{a.out, a.ldo, a.bias, a.aux, a.ldaux, a.M, a.N,
                    EPI | (a.epi & (NERF_EPI_MASKBITS | NERF_EPI_MASKOUT)), a.vec_ok};
     const bool mbits = (a.epi & NERF_EPI_MASKBITS) != 0, mout = (a.epi & NERF_EPI_MASKOUT) != 0;
@@ -707,13 +675,9 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTAr
                     if (ok && vec && GF) {
                         // pre-activation to out (kept for the backward), activation to y2
                         if (EPI & NERF_EPI_BIAS) v += bias4;
-                        if constexpr (ACT == 0)
-                            gauss_fwd_store(a.out + (int64_t)m * a.ldo + en, a.y2 + (int64_t)m * a.ldy2 + en, v, gv4);
-                        else
-                            act_fwd_store<ActFn>(a.out + (int64_t)m * a.ldo + en, a.y2 + (int64_t)m * a.ldy2 + en, v, kp);
+                        act_fwd_store<ActFn>(a.out + (int64_t)m * a.ldo + en, a.y2 + (int64_t)m * a.ldy2 + en, v, kp);
                     } else if (ok && vec && GB) {
-                        if constexpr (ACT == 0) gauss_bwd_store(a.out + (int64_t)m * a.ldo + en, v, xa[u], gv4, gp);
-                        else act_bwd_store<ActFn>(a.out + (int64_t)m * a.ldo + en, v, xa[u], kp, gp, gq);
+                        act_bwd_store<ActFn>(a.out + (int64_t)m * a.ldo + en, v, xa[u], kp, gp, gq);
                     } else if (ok && vec) {
                         float* o = a.out + (int64_t)m * a.ldo + en;
                         if (EPI & NERF_EPI_BIAS) v += bias4;
@@ -744,8 +708,8 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTAr
                 pass(32 * p, p >> 2, acc[p & 3], acc[p & 3]);
             }
         }
-        if constexpr (GB && (ACT == 0 || ActFn::kParams > 0)) {
-            // the tile's inverse-std gradient column partials: the RS row groups of each column
+        if constexpr (GB && ActFn::kParams > 0) {
+            // the tile's column partials of the first parameter's gradient: the RS row groups of each column
             // quad added in order through the free A stage, one fp64 row per 256-row tile
             double* R = reinterpret_cast<double*>(C0);
             static_assert(RS * BN * 8 <= ABYTES, "partials staging");
@@ -761,7 +725,7 @@ __global__ __launch_bounds__(512, 1) void linear_nt_x3_glds_kernel(typename NTAr
             barrier();
 #pragma unroll
             for (int e = 0; e < 4; ++e) gp[e] = 0.0;
-            if constexpr (ACT != 0 && ActFn::kParams > 1) {
+            if constexpr (ActFn::kParams > 1) {
                 // the second parameter's plane, the same way
 #pragma unroll
                 for (int e = 0; e < 4; ++e) R[erow * BN + en + e] = gq[e];
@@ -1935,6 +1899,18 @@ static const bool NT_NBLOCK = [] {
     return !(e && e[0] == '0');
 }();
 
+// Column block n0 .. n0 + 255 (or to the layer's end) of a layer: its arguments advanced to the
+// block's weights, bias and output columns
+template <class Args>
+static Args col_block(const Args& a, int n0) {
+    Args b = a;
+    b.N = a.N - n0 < 256 ? a.N - n0 : 256;
+    b.Wx = a.Wx + (size_t)n0 * 2 * a.ldw;
+    b.bias = a.bias ? a.bias + n0 : nullptr;
+    b.out = a.out + n0;
+    return b;
+}
+
 extern "C" int nerf_linear_fwd_x3(const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw,
                                   int32_t N, const float* bias, float* out, int64_t ldo, int32_t epilogue,
                                   const float* aux, int64_t ld_aux, void* stream) {
@@ -1962,11 +1938,7 @@ extern "C" int nerf_linear_fwd_x3(const nerf_seg* segs, int32_t n_segs, int64_t 
         if (grid > ntiles) grid = ntiles;
         const dim3 g3((unsigned)grid), b3(512);
         for (int n0 = 0; n0 < N; n0 += 256) {          // column blocks of <= 256 (one when N <= 256)
-            NTArgs b = a;
-            b.N = N - n0 < 256 ? N - n0 : 256;
-            b.Wx = a.Wx + (size_t)n0 * 2 * ldw;
-            b.bias = bias ? bias + n0 : nullptr;
-            b.out = out + n0;
+            NTArgs b = col_block(a, n0);
             b.aux = aux && !mbits ? aux + n0 : aux;
 #define NERF_GLDS_LAUNCH(E)                                                                            \
     do {                                                                                              \
@@ -2001,10 +1973,132 @@ extern "C" int nerf_linear_fwd_x3(const nerf_seg* segs, int32_t n_segs, int64_t 
     return NERF_OK;
 }
 
+// ------------------------------------------------------- activation epilogues (NT glds)
 extern "C" size_t nerf_linear_gauss_workspace(int64_t M, int32_t N) {
     if (M <= 0 || N <= 0) return 0;
     // one fp64 row per 128-row tile (the 256-row tile kernel uses half) + the reduction's chunk sums
-    return (size_t)((M + 127) / 128) * (size_t)N * sizeof(double) + nerf::gauss_reduce_scratch(N);
+    return (size_t)((M + 127) / 128) * (size_t)N * sizeof(double) + nerf::param_reduce_scratch(N);
+}
+
+extern "C" size_t nerf_linear_act_workspace(int32_t kind, int64_t M, int32_t N) {
+    if ((kind != NERF_ACT_GABOR && kind != NERF_ACT_SARF) || M <= 0 || N <= 0) return 0;
+    // one fp64 row per 256-row tile and learnable parameter + the reduction's chunk sums
+    return (size_t)(kind == NERF_ACT_GABOR ? 2 : 1) * (size_t)((M + 255) / 256) * (size_t)N * sizeof(double) +
+           nerf::param_reduce_scratch(N);
+}
+
+// What nerf_linear_gauss_x3 / _act_x3 / _sine_x3 differ in
+struct ActEpi {
+    int act;                  // the tile kernel's ACT
+    int params;               // learnable parameters (Fn::kParams)
+    bool chain;               // Fn::kChain
+    bool bwd256;              // the backward epilogue exists on the 256-column tile
+    const float* p[2];        // the parameters [N] and their gradients
+    float* grad[2];
+    size_t workspace;         // bytes the backward needs
+};
+template <class Fn>
+static ActEpi act_epi(bool bwd256, const float* p0, const float* p1, float* g0, float* g1, size_t workspace) {
+    return ActEpi{Fn::kKind, Fn::kParams, Fn::kChain, bwd256, {p0, p1}, {g0, g1}, workspace};
+}
+
+// BWD256 false: the backward is instantiated for the 128-column tile only (on the 256-column tile
+// Gabor's and Sarf's would spill to scratch; act_x3 refuses those layers before it gets here)
+template <int ACT, bool BWD256>
+static void launch_act_glds(const NTActArgs& b, dim3 g3, dim3 b3, hipStream_t st, int ntiles) {
+    const typename NTArgsSel<ACT>::T& k = b;
+#define NERF_ACT_LAUNCH(E)                                                                                \
+    do {                                                                                                 \
+        if (b.N > 128) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 2, ACT>), g3, b3, 0, st, k, ntiles); \
+        else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 1, ACT>), g3, b3, 0, st, k, ntiles);         \
+    } while (0)
+    if (b.epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) NERF_ACT_LAUNCH(NERF_EPI_GAUSS | NERF_EPI_BIAS);
+    else if (b.epi == NERF_EPI_GAUSS) NERF_ACT_LAUNCH(NERF_EPI_GAUSS);
+    else if constexpr (BWD256) NERF_ACT_LAUNCH(NERF_EPI_GAUSS_BWD);
+    else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS_BWD, 1, ACT>), g3, b3, 0, st, k, ntiles);
+#undef NERF_ACT_LAUNCH
+}
+
+// The one host path of the activation-epilogue GEMMs.  256-row tiles; column blocks of <= 256 (one
+// for N <= 256), each re-reading A, block n0's fp64 partials in their own [tiles][nb] slab block at
+// plane + n0 * tiles, one plane per parameter.  The Gaussian with NERF_NT_NBLOCK=0 runs layers wider
+// than 256 on the 128 x 128-tile kernel instead (one launch, one partial row per 128-row tile).
+static int act_x3(const ActEpi& d, const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw,
+                  int32_t N, const float* bias, float* out, int64_t ldo, int32_t mode, float* y, int64_t ld_y,
+                  const float* z, int64_t ld_z, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    NERF_REQUIRE(M >= 0 && M < (1ll << 31) && N >= 1 && (mode == NERF_GAUSS_FWD || mode == NERF_GAUSS_BWD));
+    NERF_REQUIRE(out != nullptr);
+    const bool fwd = mode == NERF_GAUSS_FWD;
+    if (fwd) NERF_REQUIRE(y != nullptr && ld_y >= N);
+    else NERF_REQUIRE(bias == nullptr && z != nullptr && ld_z >= N);
+    for (int p = 0; p < d.params; ++p) NERF_REQUIRE(d.p[p] != nullptr && (fwd || d.grad[p] != nullptr));
+    hipStream_t st = as_stream(stream);
+    if (M == 0) {
+        for (int p = 0; p < d.params && !fwd && !accumulate; ++p)
+            if (hipMemsetAsync(d.grad[p], 0, (size_t)N * sizeof(float), st) != hipSuccess) return NERF_ERR_LAUNCH;
+        return NERF_OK;
+    }
+    // whole 16-byte quads everywhere, or the caller takes the unfused path
+    if ((N % 4) != 0 || !aligned16(out) || (ldo % 4) != 0 || ldo < N || (bias && !aligned16(bias)) ||
+        (fwd && (!aligned16(y) || (ld_y % 4) != 0)) || (!fwd && (!aligned16(z) || (ld_z % 4) != 0)))
+        return NERF_ERR_UNSUPPORTED;
+    for (int p = 0; p < d.params; ++p)
+        if (!aligned16(d.p[p])) return NERF_ERR_UNSUPPORTED;
+    if (!fwd && N > 128 && !d.bwd256) return NERF_ERR_UNSUPPORTED;      // those layers take the separate pass
+    if (!fwd && d.params > 0 && (workspace == nullptr || workspace_bytes < d.workspace ||
+                                 (reinterpret_cast<uintptr_t>(workspace) & 7) != 0))
+        return NERF_ERR_WORKSPACE;
+    SegList L;
+    NERF_REQUIRE(build_segs(segs, n_segs, L));
+    NERF_REQUIRE(W_x && aligned16(W_x) && ldw == L.ktot && (ldw % BK) == 0);
+    const int epi = fwd ? (NERF_EPI_GAUSS | (bias ? NERF_EPI_BIAS : 0)) : NERF_EPI_GAUSS_BWD;
+    const bool tile128 = d.act == 0 && N > 256 && !NT_NBLOCK;
+    const int slabs = (int)(tile128 ? (M + 127) / 128 : (M + 255) / 256);     // row tiles = partial rows
+    const size_t plane = (size_t)slabs * (size_t)N;
+    double* part = static_cast<double*>(workspace);
+    const NTActArgs a{{L, (int)M, reinterpret_cast<const __bf16*>(W_x), ldw, N, bias, out, ldo, epi, z, ld_z, 1,
+                       d.p[0], y, ld_y, part}, d.p[1], part && d.params > 1 ? part + plane : nullptr};
+    if (tile128) {
+        const int ntiles = (slabs + 7) / 8 * 8 * ((N + 127) / 128);
+        const int cap = 2 * cu_count_x3();
+        hipLaunchKernelGGL(linear_nt_x3_kernel, dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(256), 0, st,
+                           static_cast<const NTArgs&>(a), slabs, ntiles);
+        NERF_CHECK_LAUNCH();
+        if (fwd) return NERF_OK;
+        return nerf::param_act_reduce(d.params, d.chain, part, (int64_t)plane, slabs, N, d.p[0], d.grad, accumulate,
+                                      part + plane, st);
+    }
+    const int grid = cu_count_x3() < slabs ? cu_count_x3() : slabs;
+    const dim3 g3((unsigned)grid), b3(512);
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        NTActArgs b = col_block(a, n0);
+        if (d.params > 0) b.gs = d.p[0] + n0;
+        if (d.params > 1) b.gs1 = d.p[1] + n0;
+        if (fwd) {
+            b.y2 = y + n0;
+        } else {
+            b.aux = z + n0;
+            if (d.params > 0) b.part = part + (size_t)n0 * slabs;
+            if (d.params > 1) b.part1 = part + plane + (size_t)n0 * slabs;
+        }
+        switch (d.act) {
+            case 0: launch_act_glds<0, true>(b, g3, b3, st, slabs); break;
+            case NERF_ACT_GABOR: launch_act_glds<NERF_ACT_GABOR, false>(b, g3, b3, st, slabs); break;
+            case NERF_ACT_SARF: launch_act_glds<NERF_ACT_SARF, false>(b, g3, b3, st, slabs); break;
+            default: launch_act_glds<kActSine, true>(b, g3, b3, st, slabs); break;
+        }
+        NERF_CHECK_LAUNCH();
+    }
+    if (fwd) return NERF_OK;
+    for (int n0 = 0; n0 < N && d.params > 0; n0 += 256) {
+        float* const grad[2] = {d.grad[0] + n0, d.params > 1 ? d.grad[1] + n0 : nullptr};
+        const int rc = nerf::param_act_reduce(d.params, d.chain, part + (size_t)n0 * slabs, (int64_t)plane, slabs,
+                                              N - n0 < 256 ? N - n0 : 256, d.p[0] + n0, grad, accumulate,
+                                              part + d.params * plane, st);
+        if (rc != NERF_OK) return rc;
+    }
+    return NERF_OK;
 }
 
 extern "C" int nerf_linear_gauss_x3(const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw,
@@ -2012,241 +2106,34 @@ extern "C" int nerf_linear_gauss_x3(const nerf_seg* segs, int32_t n_segs, int64_
                                     const float* inv_std, float* y, int64_t ld_y, const float* z, int64_t ld_z,
                                     float* grad_inv_std, int32_t accumulate, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-    NERF_REQUIRE(M >= 0 && M < (1ll << 31) && N >= 1 && (mode == NERF_GAUSS_FWD || mode == NERF_GAUSS_BWD));
-    NERF_REQUIRE(inv_std != nullptr && out != nullptr);
-    const bool fwd = mode == NERF_GAUSS_FWD;
-    if (fwd) NERF_REQUIRE(y != nullptr && ld_y >= N);
-    else NERF_REQUIRE(bias == nullptr && z != nullptr && ld_z >= N && grad_inv_std != nullptr);
-    hipStream_t st = as_stream(stream);
-    if (M == 0) {
-        if (!fwd && !accumulate && hipMemsetAsync(grad_inv_std, 0, (size_t)N * sizeof(float), st) != hipSuccess)
-            return NERF_ERR_LAUNCH;
-        return NERF_OK;
-    }
-    // whole 16-byte quads everywhere, or the caller takes the unfused path
-    if ((N % 4) != 0 || !aligned16(out) || (ldo % 4) != 0 || ldo < N || !aligned16(inv_std) ||
-        (bias && !aligned16(bias)) || (fwd && (!aligned16(y) || (ld_y % 4) != 0)) ||
-        (!fwd && (!aligned16(z) || (ld_z % 4) != 0)))
-        return NERF_ERR_UNSUPPORTED;
-    if (!fwd && (workspace == nullptr || workspace_bytes < nerf_linear_gauss_workspace(M, N) ||
-                 (reinterpret_cast<uintptr_t>(workspace) & 7) != 0))
-        return NERF_ERR_WORKSPACE;
-    SegList L;
-    NERF_REQUIRE(build_segs(segs, n_segs, L));
-    NERF_REQUIRE(W_x && aligned16(W_x) && ldw == L.ktot && (ldw % BK) == 0);
-    const int epi = fwd ? (NERF_EPI_GAUSS | (bias ? NERF_EPI_BIAS : 0)) : NERF_EPI_GAUSS_BWD;
-    double* part = static_cast<double*>(workspace);
-    NTArgs a{L, (int)M, reinterpret_cast<const __bf16*>(W_x), ldw, N, bias, out, ldo, epi, z, ld_z, 1,
-             inv_std, y, ld_y, part};
-    int64_t slabs;
-    if (N > 256 && NT_NBLOCK) {
-        // wider layers (GARF's Linear(3, 1024), Linear(131, 512) and the input gradients into them):
-        // column blocks of <= 256 on the 256-row tile kernel, each re-reading A, with the fp64
-        // column partials of block n0 in their own [tiles][nb] slab block (part + n0 * tiles)
-        const int ntiles = (int)((M + 255) / 256);
-        int grid = cu_count_x3();
-        if (grid > ntiles) grid = ntiles;
-        const dim3 g3((unsigned)grid), b3(512);
-        for (int n0 = 0; n0 < N; n0 += 256) {
-            NTArgs b = a;
-            b.N = N - n0 < 256 ? N - n0 : 256;
-            b.Wx = a.Wx + (size_t)n0 * 2 * ldw;
-            b.bias = bias ? bias + n0 : nullptr;
-            b.out = out + n0;
-            b.gs = inv_std + n0;
-            if (fwd) b.y2 = y + n0;
-            else b.aux = z + n0;
-            b.part = part + (size_t)n0 * ntiles;
-            if (b.N > 128) {
-                if (epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS | NERF_EPI_BIAS, 2>), g3, b3, 0, st, b, ntiles);
-                else if (epi == NERF_EPI_GAUSS) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS, 2>), g3, b3, 0, st, b, ntiles);
-                else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS_BWD, 2>), g3, b3, 0, st, b, ntiles);
-            } else {
-                if (epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS | NERF_EPI_BIAS, 1>), g3, b3, 0, st, b, ntiles);
-                else if (epi == NERF_EPI_GAUSS) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS, 1>), g3, b3, 0, st, b, ntiles);
-                else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS_BWD, 1>), g3, b3, 0, st, b, ntiles);
-            }
-            NERF_CHECK_LAUNCH();
-        }
-        if (fwd) return NERF_OK;
-        for (int n0 = 0; n0 < N; n0 += 256) {
-            const int nb = N - n0 < 256 ? N - n0 : 256;
-            const int rc = nerf::gauss_reduce(part + (size_t)n0 * ntiles, ntiles, nb, inv_std + n0, grad_inv_std + n0,
-                                              accumulate, part + (size_t)ntiles * N, st);
-            if (rc != NERF_OK) return rc;
-        }
-        return NERF_OK;
-    }
-    if (N <= 256) {
-        const int ntiles = (int)((M + 255) / 256);
-        int grid = cu_count_x3();
-        if (grid > ntiles) grid = ntiles;
-        const dim3 g3((unsigned)grid), b3(512);
-#define NERF_GLDS_LAUNCH(E)                                                                          \
-    do {                                                                                            \
-        if (N > 128) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 2>), g3, b3, 0, st, a, ntiles); \
-        else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 1>), g3, b3, 0, st, a, ntiles);         \
-    } while (0)
-        if (epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) NERF_GLDS_LAUNCH(NERF_EPI_GAUSS | NERF_EPI_BIAS);
-        else if (epi == NERF_EPI_GAUSS) NERF_GLDS_LAUNCH(NERF_EPI_GAUSS);
-        else NERF_GLDS_LAUNCH(NERF_EPI_GAUSS_BWD);
-#undef NERF_GLDS_LAUNCH
-        slabs = ntiles;
-    } else {
-        const int ntm = (int)((M + 127) / 128);
-        const int ntn = (N + 127) / 128;
-        const int ntiles = (ntm + 7) / 8 * 8 * ntn;
-        int grid = ntiles;
-        const int cap = 2 * cu_count_x3();
-        if (grid > cap) grid = cap;
-        hipLaunchKernelGGL(linear_nt_x3_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, ntm, ntiles);
-        slabs = ntm;
-    }
-    NERF_CHECK_LAUNCH();
-    if (fwd) return NERF_OK;
-    return nerf::gauss_reduce(part, slabs, N, inv_std, grad_inv_std, accumulate, part + slabs * N, st);
+    return act_x3(act_epi<GaussFn>(true, inv_std, nullptr, grad_inv_std, nullptr, nerf_linear_gauss_workspace(M, N)),
+                  segs, n_segs, M, W_x, ldw, N, bias, out, ldo, mode, y, ld_y, z, ld_z, accumulate, workspace,
+                  workspace_bytes, stream);
 }
 
-extern "C" size_t nerf_linear_act_workspace(int32_t kind, int64_t M, int32_t N) {
-    if ((kind != NERF_ACT_GABOR && kind != NERF_ACT_SARF) || M <= 0 || N <= 0) return 0;
-    // one fp64 row per 256-row tile and learnable parameter + the reduction's chunk sums
-    return (size_t)(kind == NERF_ACT_GABOR ? 2 : 1) * (size_t)((M + 255) / 256) * (size_t)N * sizeof(double) +
-           nerf::gauss_reduce_scratch(N);
-}
-
-// BWD256: the activation's backward epilogue also exists on the 256-column tile (the sine's)
-template <int ACT, bool BWD256 = false>
-static void launch_act_glds(int epi, int nb, dim3 g3, dim3 b3, hipStream_t st, const NTActArgs& b, int ntiles) {
-#define NERF_ACT_LAUNCH(E)                                                                                \
-    do {                                                                                                 \
-        if (nb > 128) hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 2, ACT>), g3, b3, 0, st, b, ntiles); \
-        else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<E, 1, ACT>), g3, b3, 0, st, b, ntiles);         \
-    } while (0)
-    if (epi == (NERF_EPI_GAUSS | NERF_EPI_BIAS)) NERF_ACT_LAUNCH(NERF_EPI_GAUSS | NERF_EPI_BIAS);
-    else if (epi == NERF_EPI_GAUSS) NERF_ACT_LAUNCH(NERF_EPI_GAUSS);
-    // Gabor / Sarf: the backward exists for 128-column tiles only (nerf_linear_act_x3 refuses wider ones)
-    else if constexpr (BWD256) NERF_ACT_LAUNCH(NERF_EPI_GAUSS_BWD);
-    else hipLaunchKernelGGL((linear_nt_x3_glds_kernel<NERF_EPI_GAUSS_BWD, 1, ACT>), g3, b3, 0, st, b, ntiles);
-#undef NERF_ACT_LAUNCH
-}
-
+// Gabor / Sarf: the backward epilogue on the 256-column tile needs more registers than the kernel
+// has (it would spill to scratch), so the backward is refused for N > 128
 extern "C" int nerf_linear_act_x3(int32_t kind, const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x,
                                   int32_t ldw, int32_t N, const float* bias, float* out, int64_t ldo, int32_t mode,
                                   const float* p0, const float* p1, float* y, int64_t ld_y, const float* z,
                                   int64_t ld_z, float* grad_p0, float* grad_p1, int32_t accumulate, void* workspace,
                                   size_t workspace_bytes, void* stream) {
     NERF_REQUIRE(kind == NERF_ACT_GABOR || kind == NERF_ACT_SARF);
-    const bool two = kind == NERF_ACT_GABOR;
-    NERF_REQUIRE(M >= 0 && M < (1ll << 31) && N >= 1 && (mode == NERF_GAUSS_FWD || mode == NERF_GAUSS_BWD));
-    NERF_REQUIRE(p0 != nullptr && (!two || p1 != nullptr) && out != nullptr);
-    const bool fwd = mode == NERF_GAUSS_FWD;
-    if (fwd) NERF_REQUIRE(y != nullptr && ld_y >= N);
-    else NERF_REQUIRE(bias == nullptr && z != nullptr && ld_z >= N && grad_p0 != nullptr &&
-                      (!two || grad_p1 != nullptr));
-    hipStream_t st = as_stream(stream);
-    if (M == 0) {
-        if (!fwd && !accumulate) {
-            if (hipMemsetAsync(grad_p0, 0, (size_t)N * sizeof(float), st) != hipSuccess) return NERF_ERR_LAUNCH;
-            if (two && hipMemsetAsync(grad_p1, 0, (size_t)N * sizeof(float), st) != hipSuccess)
-                return NERF_ERR_LAUNCH;
-        }
-        return NERF_OK;
-    }
-    // whole 16-byte quads everywhere, or the caller takes the unfused path
-    if ((N % 4) != 0 || !aligned16(out) || (ldo % 4) != 0 || ldo < N || !aligned16(p0) || (two && !aligned16(p1)) ||
-        (bias && !aligned16(bias)) || (fwd && (!aligned16(y) || (ld_y % 4) != 0)) ||
-        (!fwd && (!aligned16(z) || (ld_z % 4) != 0)))
-        return NERF_ERR_UNSUPPORTED;
-    // the backward epilogue on the 256-column tile needs more registers than the kernel has
-    // (it would spill to scratch): those layers take the separate activation pass
-    if (!fwd && N > 128) return NERF_ERR_UNSUPPORTED;
-    if (!fwd && (workspace == nullptr || workspace_bytes < nerf_linear_act_workspace(kind, M, N) ||
-                 (reinterpret_cast<uintptr_t>(workspace) & 7) != 0))
-        return NERF_ERR_WORKSPACE;
-    SegList L;
-    NERF_REQUIRE(build_segs(segs, n_segs, L));
-    NERF_REQUIRE(W_x && aligned16(W_x) && ldw == L.ktot && (ldw % BK) == 0);
-    const int epi = fwd ? (NERF_EPI_GAUSS | (bias ? NERF_EPI_BIAS : 0)) : NERF_EPI_GAUSS_BWD;
-    // 256-row tiles; column blocks of <= 256 (one for N <= 256), block n0's fp64 partials in their
-    // own [tiles][nb] slab block at plane + n0 * tiles, one plane per parameter
-    const int ntiles = (int)((M + 255) / 256);
-    const size_t plane = (size_t)ntiles * (size_t)N;
-    double* part = static_cast<double*>(workspace);
-    NTActArgs a{{L, (int)M, reinterpret_cast<const __bf16*>(W_x), ldw, N, bias, out, ldo, epi, z, ld_z, 1,
-                 p0, y, ld_y, part}, p1, part ? part + plane : nullptr};
-    int grid = cu_count_x3();
-    if (grid > ntiles) grid = ntiles;
-    const dim3 g3((unsigned)grid), b3(512);
-    for (int n0 = 0; n0 < N; n0 += 256) {
-        NTActArgs b = a;
-        b.N = N - n0 < 256 ? N - n0 : 256;
-        b.Wx = a.Wx + (size_t)n0 * 2 * ldw;
-        b.bias = bias ? bias + n0 : nullptr;
-        b.out = out + n0;
-        b.gs = p0 + n0;
-        b.gs1 = two ? p1 + n0 : nullptr;
-        if (fwd) {
-            b.y2 = y + n0;
-        } else {
-            b.aux = z + n0;
-            b.part = part + (size_t)n0 * ntiles;
-            b.part1 = part + plane + (size_t)n0 * ntiles;
-        }
-        if (two) launch_act_glds<NERF_ACT_GABOR>(epi, b.N, g3, b3, st, b, ntiles);
-        else launch_act_glds<NERF_ACT_SARF>(epi, b.N, g3, b3, st, b, ntiles);
-        NERF_CHECK_LAUNCH();
-    }
-    if (fwd) return NERF_OK;
-    double* scratch = part + (two ? 2 : 1) * plane;
-    for (int n0 = 0; n0 < N; n0 += 256) {
-        const int nb = N - n0 < 256 ? N - n0 : 256;
-        const int rc = nerf::param_act_reduce(kind, part + (size_t)n0 * ntiles, (int64_t)plane, ntiles, nb, p0 + n0,
-                                              grad_p0 + n0, two ? grad_p1 + n0 : nullptr, accumulate, scratch, st);
-        if (rc != NERF_OK) return rc;
-    }
-    return NERF_OK;
+    const size_t need = nerf_linear_act_workspace(kind, M, N);
+    return act_x3(kind == NERF_ACT_GABOR ? act_epi<GaborFn>(false, p0, p1, grad_p0, grad_p1, need)
+                                         : act_epi<SarfFn>(false, p0, p1, grad_p0, grad_p1, need),
+                  segs, n_segs, M, W_x, ldw, N, bias, out, ldo, mode, y, ld_y, z, ld_z, accumulate, workspace,
+                  workspace_bytes, stream);
 }
 
-// nerf_linear_act_x3 with SIREN's sine (SineFn): no parameters, so no partial planes, no reduce
-// and no workspace.  Unlike Gabor / Sarf its backward epilogue (one sincos and one multiply per
-// element, no fp64 column sums) also runs on the 256-column tile.
+// SIREN's sine: no parameters, so no partial planes, no reduce and no workspace.  Its backward
+// epilogue (one sincos and one multiply per element, no fp64 column sums) also runs on the
+// 256-column tile.
 extern "C" int nerf_linear_sine_x3(const nerf_seg* segs, int32_t n_segs, int64_t M, const void* W_x, int32_t ldw,
                                    int32_t N, const float* bias, float* out, int64_t ldo, int32_t mode, float* y,
                                    int64_t ld_y, const float* z, int64_t ld_z, void* stream) {
-    NERF_REQUIRE(M >= 0 && M < (1ll << 31) && N >= 1 && (mode == NERF_GAUSS_FWD || mode == NERF_GAUSS_BWD));
-    NERF_REQUIRE(out != nullptr);
-    const bool fwd = mode == NERF_GAUSS_FWD;
-    if (fwd) NERF_REQUIRE(y != nullptr && ld_y >= N);
-    else NERF_REQUIRE(bias == nullptr && z != nullptr && ld_z >= N);
-    if (M == 0) return NERF_OK;
-    // whole 16-byte quads everywhere, or the caller takes the unfused path
-    if ((N % 4) != 0 || !aligned16(out) || (ldo % 4) != 0 || ldo < N || (bias && !aligned16(bias)) ||
-        (fwd && (!aligned16(y) || (ld_y % 4) != 0)) || (!fwd && (!aligned16(z) || (ld_z % 4) != 0)))
-        return NERF_ERR_UNSUPPORTED;
-    SegList L;
-    NERF_REQUIRE(build_segs(segs, n_segs, L));
-    NERF_REQUIRE(W_x && aligned16(W_x) && ldw == L.ktot && (ldw % BK) == 0);
-    const int epi = fwd ? (NERF_EPI_GAUSS | (bias ? NERF_EPI_BIAS : 0)) : NERF_EPI_GAUSS_BWD;
-    hipStream_t st = as_stream(stream);
-    // 256-row tiles; column blocks of <= 256 (one for N <= 256)
-    const int ntiles = (int)((M + 255) / 256);
-    NTActArgs a{{L, (int)M, reinterpret_cast<const __bf16*>(W_x), ldw, N, bias, out, ldo, epi, z, ld_z, 1,
-                 nullptr, y, ld_y, nullptr}, nullptr, nullptr};
-    int grid = cu_count_x3();
-    if (grid > ntiles) grid = ntiles;
-    const dim3 g3((unsigned)grid), b3(512);
-    for (int n0 = 0; n0 < N; n0 += 256) {
-        NTActArgs b = a;
-        b.N = N - n0 < 256 ? N - n0 : 256;
-        b.Wx = a.Wx + (size_t)n0 * 2 * ldw;
-        b.bias = bias ? bias + n0 : nullptr;
-        b.out = out + n0;
-        if (fwd) b.y2 = y + n0;
-        else b.aux = z + n0;
-        launch_act_glds<kActSine, true>(epi, b.N, g3, b3, st, b, ntiles);
-        NERF_CHECK_LAUNCH();
-    }
-    return NERF_OK;
+    return act_x3(act_epi<SineFn>(true, nullptr, nullptr, nullptr, nullptr, 0), segs, n_segs, M, W_x, ldw, N, bias,
+                  out, ldo, mode, y, ld_y, z, ld_z, 0, nullptr, 0, stream);
 }
 
 // NERF_WGRAD_SMALLN=0: layers with N <= 16 on the 128-tile kernel (A/B switch, read once)

@@ -1,9 +1,16 @@
-// Per-element formulas of the learnable per-channel activations next to GARF's Gaussian:
+// Per-element formulas of the per-channel activations, one functor each (load, fwd, bwd, kParams):
+//   Gauss  garf/gaussian.py:8-63  (GaussActivation autograd, GaussAct; copy in barf/gaussian.py)
 //   Gabor  gaborf/gabor.py:8-64   (GaborActivation autograd, GaborAct)
 //   Sarf   sarf/activation.py:40-65 (SarfAct.forward, the cos * exp form it returns)
+//   Sine   nerf-siren/linear_sine.py:44-45  (the activation of LinearSine; no parameters)
 // The stand-alone kernels (param_act.hip) and the GEMM epilogues (linear_x3.hip) call the same
 // functions, so the two routes differ only in the summation order of the column partials.
 //
+// Gauss, v = s^2 + 1e-6 (s = inv_standard_deviation):
+//   forward   y  = exp((-(z*z)) * v)
+//   backward  ge = g * exp((-(z*z)) * v)
+//             dz = (((-ge) * 2) * z) * v
+//             dv_n = sum_m (-ge) * z^2               ds_n = dv_n * (2 * s_n)
 // Gabor, v = s^2 + 1e-6 (s = inv_standard_deviation, p = spread):
 //   forward   y  = exp((-(z*z)) * v) * cos(p*z)
 //   backward  go = (-exp((-(z*z)) * v)) * g
@@ -22,7 +29,9 @@
 // single exp whose argument error is relative to y.  Gabor takes the exact product p z as
 // hi + lo (one FMA); Sarf forms t, q and f / q in fp64 and splits the quotient.  Everything else
 // is fp32 arithmetic in the order written above.
-//   Sine   nerf-siren/linear_sine.py:44-45  (the activation of LinearSine; no parameters)
+//
+// kChain: the first parameter is s of v = s^2 + 1e-6, so its column sum (dv) is finished with the
+// chain-rule factor 2 s (param_reduce).
 #pragma once
 #include "common.h"
 
@@ -37,9 +46,34 @@ __device__ __forceinline__ void sincos_arg(float hi, float lo, float* s, float* 
     *c = __builtin_fmaf(-s0, lo, c0);
 }
 
+// GARF's Gaussian.  kKind is the tile GEMM's template value 0; no public `kind` takes it.
+struct GaussFn {
+    static constexpr int kKind = 0;
+    static constexpr int kParams = 1;
+    static constexpr bool kChain = true;
+    struct P { float v; };
+    static __device__ __forceinline__ P load(const float* p0, const float*, int n) {
+#pragma clang fp contract(off)
+        const float sv = p0[n];
+        return P{sv * sv + 1e-6f};
+    }
+    static __device__ __forceinline__ float fwd(float z, P k) {
+#pragma clang fp contract(off)
+        return expf((-(z * z)) * k.v);
+    }
+    static __device__ __forceinline__ float bwd(float g, float z, P k, double& a0, double&) {
+#pragma clang fp contract(off)
+        const float z2 = z * z;
+        const float ge = g * expf((-z2) * k.v);
+        a0 += (double)((-ge) * z2);
+        return (((-ge) * 2.0f) * z) * k.v;
+    }
+};
+
 struct GaborFn {
     static constexpr int kKind = NERF_ACT_GABOR;
     static constexpr int kParams = 2;
+    static constexpr bool kChain = true;
     struct P { float v, p; };
     static __device__ __forceinline__ P load(const float* p0, const float* p1, int n) {
 #pragma clang fp contract(off)
@@ -69,6 +103,7 @@ struct GaborFn {
 struct SarfFn {
     static constexpr int kKind = NERF_ACT_SARF;
     static constexpr int kParams = 1;
+    static constexpr bool kChain = false;
     struct P { float f, r; double rd; };          // frequency, 1 / (f * f) in fp32 and in fp64
     static __device__ __forceinline__ P load(const float* p0, const float*, int n) {
 #pragma clang fp contract(off)
@@ -113,6 +148,7 @@ struct SarfFn {
 struct SineFn {
     static constexpr int kKind = 3;
     static constexpr int kParams = 0;
+    static constexpr bool kChain = false;
     struct P {};
     static __device__ __forceinline__ P load(const float*, const float*, int) { return P{}; }
     static __device__ __forceinline__ float fwd(float z, P) {
@@ -128,15 +164,17 @@ struct SineFn {
     }
 };
 
-// Column sums of per-slab fp64 partials [slabs][N] as nerf::gauss_reduce forms them (same two
-// fixed-order levels, same scratch), finished without the chain-rule factor:
-// dp_n (+)= (float)(sum_i partial[i][n]).  For Gabor's spread and Sarf's frequency.
-int param_reduce_plain(const double* partial, int64_t slabs, int N, float* dp, int accumulate, double* scratch,
-                       hipStream_t stream);
+// Column sums of per-slab fp64 partials [slabs][N], in a fixed order (chunks of slabs in parallel,
+// 4 strided runs each combined in order, then the chunks in order): dp_n (+)= (float)(sum_i
+// partial[i][n]), times (2 * s_n) when s is given (the gradient of s from that of v = s^2 + 1e-6).
+// scratch holds param_reduce_scratch(N) bytes.
+size_t param_reduce_scratch(int N);
+int param_reduce(const double* partial, int64_t slabs, int N, const float* s, float* dp, int accumulate,
+                 double* scratch, hipStream_t stream);
 
-// Both parameter gradients of one activation from its partial planes (plane p at
-// partial + p * plane): Gabor's s through nerf::gauss_reduce, the others through the plain sum.
-int param_act_reduce(int kind, const double* partial, int64_t plane, int64_t slabs, int N, const float* p0,
-                     float* grad_p0, float* grad_p1, int accumulate, double* scratch, hipStream_t stream);
+// All `params` parameter gradients of one activation from its partial planes (plane p at
+// partial + p * plane); chain: the first one takes the factor 2 * p0.
+int param_act_reduce(int params, bool chain, const double* partial, int64_t plane, int64_t slabs, int N,
+                     const float* p0, float* const* grad, int accumulate, double* scratch, hipStream_t stream);
 
 }  // namespace nerf

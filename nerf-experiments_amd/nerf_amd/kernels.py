@@ -377,34 +377,37 @@ def adam_step(entries, beta1: float, beta2: float, eps: float, device) -> None:
         _lib.check(lib.nerf_adam_step(ctypes.byref(b), _stream(device)), "nerf_adam_step")
 
 
-# ----------------------------------------------------------------------------- gaussian activation
-def gauss_act_fwd(z: torch.Tensor, N: int, inv_std: torch.Tensor, y: torch.Tensor) -> None:
-    _require_cuda_f32("inv_standard_deviation", inv_std)
-    end = TIMER.bracket("gauss_act_fwd", 0.0, 8.0 * z.shape[0] * N, fn="gauss_fwd_kernel") \
-        if TIMER is not None else None
-    st = _lib.load().nerf_gauss_act_fwd(_ptr(z), z.stride(0), _ptr(inv_std), z.shape[0], N, _ptr(y), y.stride(0),
-                                        _stream(z.device))
+# ------------------------------------------------- per-channel activations (param_act.hip)
+# GARF's Gaussian, Gabor / Sarf and SIREN's sine as stand-alone passes: one kernel pair,
+# param_act_fwd_kernel / param_act_bwd_kernel, instantiated per activation.
+def _act_pass(name: str, traffic: float, device, *args) -> None:
+    """nerf_<name>(*args, stream) inside the timer's bracket `name` (an _act_fwd / _act_bwd pass)."""
+    fn = "param_act_fwd_kernel" if name.endswith("fwd") else "param_act_bwd_kernel"
+    end = TIMER.bracket(name, 0.0, traffic, fn=fn) if TIMER is not None else None
+    st = getattr(_lib.load(), "nerf_" + name)(*args, _stream(device))
     if end is not None:
         end.record()
-    _lib.check(st, "nerf_gauss_act_fwd")
+    _lib.check(st, "nerf_" + name)
+
+
+def _f64_workspace(nbytes: int, device) -> torch.Tensor:
+    return torch.empty(max(1, (int(nbytes) + 7) // 8), device=device, dtype=torch.float64)
+
+
+def gauss_act_fwd(z: torch.Tensor, N: int, inv_std: torch.Tensor, y: torch.Tensor) -> None:
+    _require_cuda_f32("inv_standard_deviation", inv_std)
+    _act_pass("gauss_act_fwd", 8.0 * z.shape[0] * N, z.device, _ptr(z), z.stride(0), _ptr(inv_std), z.shape[0], N,
+              _ptr(y), y.stride(0))
 
 
 def gauss_act_bwd(grad_y: torch.Tensor, z: torch.Tensor, N: int, inv_std: torch.Tensor, grad_z: torch.Tensor,
                   grad_inv_std: torch.Tensor) -> None:
     M = z.shape[0]
-    lib = _lib.load()
-    ws = torch.empty(max(1, (int(lib.nerf_gauss_act_workspace(M, N)) + 7) // 8), device=z.device,
-                     dtype=torch.float64)
-    end = TIMER.bracket("gauss_act_bwd", 0.0, 12.0 * M * N, fn="gauss_bwd_kernel") if TIMER is not None else None
-    st = lib.nerf_gauss_act_bwd(_ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0), _ptr(inv_std), M, N,
-                                _ptr(grad_z), grad_z.stride(0), _ptr(grad_inv_std), 0, _ptr(ws),
-                                ws.numel() * 8, _stream(z.device))
-    if end is not None:
-        end.record()
-    _lib.check(st, "nerf_gauss_act_bwd")
+    ws = _f64_workspace(_lib.load().nerf_gauss_act_workspace(M, N), z.device)
+    _act_pass("gauss_act_bwd", 12.0 * M * N, z.device, _ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0),
+              _ptr(inv_std), M, N, _ptr(grad_z), grad_z.stride(0), _ptr(grad_inv_std), 0, _ptr(ws), ws.numel() * 8)
 
 
-# ------------------------------------------------------------- Gabor / Sarf activations (param_act.hip)
 # kind: _lib.NERF_ACT_GABOR (params = (inv_standard_deviation, spread)) or _lib.NERF_ACT_SARF
 # (params = (frequency,)); the gradients come in the same order
 _ACT_PARAMS = {_lib.NERF_ACT_GABOR: 2, _lib.NERF_ACT_SARF: 1}
@@ -420,52 +423,30 @@ def _act_ptrs(kind: int, params, what: str = "activation parameters"):
 
 def param_act_fwd(kind: int, z: torch.Tensor, N: int, params, y: torch.Tensor) -> None:
     p0, p1 = _act_ptrs(kind, params)
-    end = TIMER.bracket("param_act_fwd", 0.0, 8.0 * z.shape[0] * N, fn="param_act_fwd_kernel") \
-        if TIMER is not None else None
-    st = _lib.load().nerf_param_act_fwd(kind, _ptr(z), z.stride(0), p0, p1, z.shape[0], N, _ptr(y), y.stride(0),
-                                        _stream(z.device))
-    if end is not None:
-        end.record()
-    _lib.check(st, "nerf_param_act_fwd")
+    _act_pass("param_act_fwd", 8.0 * z.shape[0] * N, z.device, kind, _ptr(z), z.stride(0), p0, p1, z.shape[0], N,
+              _ptr(y), y.stride(0))
 
 
 def param_act_bwd(kind: int, grad_y: torch.Tensor, z: torch.Tensor, N: int, params, grad_z: torch.Tensor,
                   grads, accumulate: bool = False) -> None:
     M = z.shape[0]
-    lib = _lib.load()
     p0, p1 = _act_ptrs(kind, params)
     g0, g1 = _act_ptrs(kind, grads, "activation parameter gradients")
-    ws = torch.empty(max(1, (int(lib.nerf_param_act_workspace(kind, M, N)) + 7) // 8), device=z.device,
-                     dtype=torch.float64)
-    end = TIMER.bracket("param_act_bwd", 0.0, 12.0 * M * N, fn="param_act_bwd_kernel") if TIMER is not None else None
-    st = lib.nerf_param_act_bwd(kind, _ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0), p0, p1, M, N,
-                                _ptr(grad_z), grad_z.stride(0), g0, g1, int(accumulate), _ptr(ws), ws.numel() * 8,
-                                _stream(z.device))
-    if end is not None:
-        end.record()
-    _lib.check(st, "nerf_param_act_bwd")
+    ws = _f64_workspace(_lib.load().nerf_param_act_workspace(kind, M, N), z.device)
+    _act_pass("param_act_bwd", 12.0 * M * N, z.device, kind, _ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0),
+              p0, p1, M, N, _ptr(grad_z), grad_z.stride(0), g0, g1, int(accumulate), _ptr(ws), ws.numel() * 8)
 
 
-# ------------------------------------------------------------------ SIREN's sine (param_act.hip)
 def sine_act_fwd(z: torch.Tensor, N: int, y: torch.Tensor) -> None:
     """y[:, :N] = sin(z[:, :N]) (nerf_sine_act_fwd)."""
-    end = TIMER.bracket("sine_act_fwd", 0.0, 8.0 * z.shape[0] * N, fn="param_act_fwd_kernel") \
-        if TIMER is not None else None
-    st = _lib.load().nerf_sine_act_fwd(_ptr(z), z.stride(0), z.shape[0], N, _ptr(y), y.stride(0), _stream(z.device))
-    if end is not None:
-        end.record()
-    _lib.check(st, "nerf_sine_act_fwd")
+    _act_pass("sine_act_fwd", 8.0 * z.shape[0] * N, z.device, _ptr(z), z.stride(0), z.shape[0], N, _ptr(y),
+              y.stride(0))
 
 
 def sine_act_bwd(grad_y: torch.Tensor, z: torch.Tensor, N: int, grad_z: torch.Tensor) -> None:
     """grad_z[:, :N] = grad_y[:, :N] * cos(z[:, :N]) (nerf_sine_act_bwd; grad_z may be grad_y)."""
-    end = TIMER.bracket("sine_act_bwd", 0.0, 12.0 * z.shape[0] * N, fn="sine_act_bwd_kernel") \
-        if TIMER is not None else None
-    st = _lib.load().nerf_sine_act_bwd(_ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0), z.shape[0], N,
-                                       _ptr(grad_z), grad_z.stride(0), _stream(z.device))
-    if end is not None:
-        end.record()
-    _lib.check(st, "nerf_sine_act_bwd")
+    _act_pass("sine_act_bwd", 12.0 * z.shape[0] * N, z.device, _ptr(grad_y), grad_y.stride(0), _ptr(z), z.stride(0),
+              z.shape[0], N, _ptr(grad_z), grad_z.stride(0))
 
 
 # ----------------------------------------------------------------------------- linear layers
@@ -564,6 +545,35 @@ def linear_fwd_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, bias: torch.
     _lib.check(st, "nerf_linear_fwd_x3")
 
 
+def _linear_epilogue_x3(name: str, segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.Tensor, bias, y, z,
+                        w_row_offset: int, fn: str, launches: int, params=(), grads=(None, None),
+                        workspace_bytes=None, kind=()) -> bool:
+    """nerf_linear_<name>_x3: forward when y is given, else the input gradient (z given).  params:
+    the C function's parameter pointers, grads: its two gradient arguments (none of either for the
+    sine), workspace_bytes(): the backward's.  False when the library refuses the shapes."""
+    arr = make_segs(segs)
+    off = w_row_offset * ldw * 2 * 2
+    fwd = y is not None
+    ws = None
+    if not fwd and workspace_bytes is not None:
+        ws = _f64_workspace(workspace_bytes(), out.device)
+    nbytes = _segs_bytes(segs, M) + 4.0 * N * ldw + (8.0 * M * N if fwd else 12.0 * M * N)
+    end = TIMER.bracket(f"linear_{name}_x3" if fwd else f"linear_{name}_bwd_x3", 2.0 * M * N * ldw, nbytes,
+                        fn=fn, launches=launches) if TIMER is not None else None
+    cname = f"nerf_linear_{name}_x3"
+    tail = (*grads, 0, _ptr(ws), ws.numel() * 8 if ws is not None else 0) if workspace_bytes is not None else ()
+    st = getattr(_lib.load(), cname)(*kind, arr, len(segs), M, Wx.data_ptr() + off, ldw, N, _ptr(bias), _ptr(out),
+                                     out.stride(0), _lib.NERF_GAUSS_FWD if fwd else _lib.NERF_GAUSS_BWD, *params,
+                                     _ptr(y), y.stride(0) if fwd else 0, _ptr(z),
+                                     z.stride(0) if z is not None else 0, *tail, _stream(out.device))
+    if end is not None:
+        end.record()
+    if st == _lib.NERF_ERR_UNSUPPORTED:
+        return False
+    _lib.check(st, cname)
+    return True
+
+
 def linear_gauss_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.Tensor, inv_std: torch.Tensor, *,
                     bias: torch.Tensor | None = None, y: torch.Tensor | None = None, z: torch.Tensor | None = None,
                     grad_inv_std: torch.Tensor | None = None, w_row_offset: int = 0) -> bool:
@@ -573,29 +583,9 @@ def linear_gauss_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch
     from the product (= dL/dy), and grad_inv_std = its inverse-std gradient.  Returns False when the
     shapes need the unfused path (N % 4, alignment)."""
     _require_cuda_f32("inv_standard_deviation", inv_std)
-    arr = make_segs(segs)
-    off = w_row_offset * ldw * 2 * 2
-    fwd = y is not None
-    lib = _lib.load()
-    ws = None
-    if not fwd:
-        ws = torch.empty(max(1, (int(lib.nerf_linear_gauss_workspace(M, N)) + 7) // 8), device=out.device,
-                         dtype=torch.float64)
-    nbytes = _segs_bytes(segs, M) + 4.0 * N * ldw + (8.0 * M * N if fwd else 12.0 * M * N)
-    end = TIMER.bracket("linear_gauss_x3" if fwd else "linear_gauss_bwd_x3", 2.0 * M * N * ldw, nbytes,
-                        fn=_nt_x3_fn(N), launches=_nt_x3_launches(N)) \
-        if TIMER is not None else None
-    st = lib.nerf_linear_gauss_x3(arr, len(segs), M, Wx.data_ptr() + off, ldw, N, _ptr(bias), _ptr(out),
-                                  out.stride(0), _lib.NERF_GAUSS_FWD if fwd else _lib.NERF_GAUSS_BWD,
-                                  _ptr(inv_std), _ptr(y), y.stride(0) if fwd else 0, _ptr(z),
-                                  z.stride(0) if z is not None else 0, _ptr(grad_inv_std), 0, _ptr(ws),
-                                  ws.numel() * 8 if ws is not None else 0, _stream(out.device))
-    if end is not None:
-        end.record()
-    if st == _lib.NERF_ERR_UNSUPPORTED:
-        return False
-    _lib.check(st, "nerf_linear_gauss_x3")
-    return True
+    return _linear_epilogue_x3("gauss", segs, M, Wx, ldw, N, out, bias, y, z, w_row_offset, _nt_x3_fn(N),
+                               _nt_x3_launches(N), (_ptr(inv_std),), (_ptr(grad_inv_std),),
+                               lambda: _lib.load().nerf_linear_gauss_workspace(M, N))
 
 
 def linear_act_x3(kind: int, segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.Tensor, params, *,
@@ -605,31 +595,11 @@ def linear_act_x3(kind: int, segs, M: int, Wx: torch.Tensor, ldw: int, N: int, o
     out = z = x W^T + b, y = act(z); input gradient (z, grads given) out = dL/dz from the product
     (= dL/dy), grads = the activation parameters' gradients.  Returns False when the shapes need
     the unfused path (N % 4, alignment)."""
-    p0, p1 = _act_ptrs(kind, params)
-    arr = make_segs(segs)
-    off = w_row_offset * ldw * 2 * 2
-    fwd = y is not None
-    lib = _lib.load()
-    ws = None
-    g0 = g1 = None
-    if not fwd:
-        g0, g1 = _act_ptrs(kind, grads, "activation parameter gradients")
-        ws = torch.empty(max(1, (int(lib.nerf_linear_act_workspace(kind, M, N)) + 7) // 8), device=out.device,
-                         dtype=torch.float64)
-    nbytes = _segs_bytes(segs, M) + 4.0 * N * ldw + (8.0 * M * N if fwd else 12.0 * M * N)
-    end = TIMER.bracket("linear_act_x3" if fwd else "linear_act_bwd_x3", 2.0 * M * N * ldw, nbytes,
-                        fn="linear_nt_x3_glds_kernel", launches=(N + 255) // 256) \
-        if TIMER is not None else None
-    st = lib.nerf_linear_act_x3(kind, arr, len(segs), M, Wx.data_ptr() + off, ldw, N, _ptr(bias), _ptr(out),
-                                out.stride(0), _lib.NERF_GAUSS_FWD if fwd else _lib.NERF_GAUSS_BWD, p0, p1,
-                                _ptr(y), y.stride(0) if fwd else 0, _ptr(z), z.stride(0) if z is not None else 0,
-                                g0, g1, 0, _ptr(ws), ws.numel() * 8 if ws is not None else 0, _stream(out.device))
-    if end is not None:
-        end.record()
-    if st == _lib.NERF_ERR_UNSUPPORTED:
-        return False
-    _lib.check(st, "nerf_linear_act_x3")
-    return True
+    pptrs = _act_ptrs(kind, params)
+    gptrs = (None, None) if y is not None else _act_ptrs(kind, grads, "activation parameter gradients")
+    return _linear_epilogue_x3("act", segs, M, Wx, ldw, N, out, bias, y, z, w_row_offset, "linear_nt_x3_glds_kernel",
+                               (N + 255) // 256, pptrs, gptrs,
+                               lambda: _lib.load().nerf_linear_act_workspace(kind, M, N), (kind,))
 
 
 def linear_sine_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.Tensor, *,
@@ -638,23 +608,8 @@ def linear_sine_x3(segs, M: int, Wx: torch.Tensor, ldw: int, N: int, out: torch.
     """linear_act_x3 for SIREN's sine (nerf_linear_sine_x3): forward (y given) out = z = x W^T + b,
     y = sin(z); input gradient (z given) out = dL/dz = (the product, dL/dy) * cos(z).  Returns False
     when the shapes need the unfused path (N % 4, alignment)."""
-    arr = make_segs(segs)
-    off = w_row_offset * ldw * 2 * 2
-    fwd = y is not None
-    nbytes = _segs_bytes(segs, M) + 4.0 * N * ldw + (8.0 * M * N if fwd else 12.0 * M * N)
-    end = TIMER.bracket("linear_sine_x3" if fwd else "linear_sine_bwd_x3", 2.0 * M * N * ldw, nbytes,
-                        fn="linear_nt_x3_glds_kernel", launches=(N + 255) // 256) \
-        if TIMER is not None else None
-    st = _lib.load().nerf_linear_sine_x3(arr, len(segs), M, Wx.data_ptr() + off, ldw, N, _ptr(bias), _ptr(out),
-                                         out.stride(0), _lib.NERF_GAUSS_FWD if fwd else _lib.NERF_GAUSS_BWD,
-                                         _ptr(y), y.stride(0) if fwd else 0, _ptr(z),
-                                         z.stride(0) if z is not None else 0, _stream(out.device))
-    if end is not None:
-        end.record()
-    if st == _lib.NERF_ERR_UNSUPPORTED:
-        return False
-    _lib.check(st, "nerf_linear_sine_x3")
-    return True
+    return _linear_epilogue_x3("sine", segs, M, Wx, ldw, N, out, bias, y, z, w_row_offset, "linear_nt_x3_glds_kernel",
+                               (N + 255) // 256)
 
 
 def quad_split_pack(x: torch.Tensor) -> torch.Tensor:

@@ -160,6 +160,26 @@ def test_argument_validation_returns_status_without_launch():
     assert lib.nerf_linear_gauss_x3(None, 0, 10, 256, 32, 8, None, 256, 8, 1, 256, None, 0, 256, 8, 256, 0,
                                     None, 0, None) == -4
     assert lib.nerf_linear_gauss_workspace(1000, 64) >= 8 * 64 * 8
+    # the same four for the Gabor / Sarf epilogue, whose backward is also refused for N = 132 (> 128)
+    # before its workspace is looked at; kind 0 is no kind
+    for kind in (_lib.NERF_ACT_GABOR, _lib.NERF_ACT_SARF):
+        assert lib.nerf_linear_act_x3(kind, None, 0, 10, 256, 32, 8, None, 256, 8, 2, 256, 256, 256, 8, None, 0,
+                                      None, None, 0, None, 0, None) == -1
+        assert lib.nerf_linear_act_x3(kind, None, 0, 0, 256, 32, 8, None, 256, 8, 0, 256, 256, 256, 8, None, 0,
+                                      None, None, 0, None, 0, None) == 0
+        assert lib.nerf_linear_act_x3(kind, None, 0, 10, 256, 32, 6, None, 256, 8, 0, 256, 256, 256, 8, None, 0,
+                                      None, None, 0, None, 0, None) == -2
+        assert lib.nerf_linear_act_x3(kind, None, 0, 10, 256, 32, 8, None, 256, 8, 1, 256, 256, None, 0, 256, 8,
+                                      256, 256, 0, None, 0, None) == -4
+        assert lib.nerf_linear_act_x3(kind, None, 0, 10, 256, 32, 132, None, 256, 132, 1, 256, 256, None, 0, 256,
+                                      132, 256, 256, 0, 256, 1 << 20, None) == -2
+    assert lib.nerf_linear_act_x3(0, None, 0, 10, 256, 32, 8, None, 256, 8, 0, 256, 256, 256, 8, None, 0,
+                                  None, None, 0, None, 0, None) == -1
+    # and for the sine epilogue, whose backward takes no workspace: it gets as far as the (missing) segments
+    assert lib.nerf_linear_sine_x3(None, 0, 10, 256, 32, 8, None, 256, 8, 2, 256, 8, None, 0, None) == -1
+    assert lib.nerf_linear_sine_x3(None, 0, 0, 256, 32, 8, None, 256, 8, 0, 256, 8, None, 0, None) == 0
+    assert lib.nerf_linear_sine_x3(None, 0, 10, 256, 32, 6, None, 256, 8, 0, 256, 8, None, 0, None) == -2
+    assert lib.nerf_linear_sine_x3(None, 0, 10, 256, 32, 8, None, 256, 8, 1, None, 0, 256, 8, None) == -1
     # Kabsch: too few / too many points, missing outputs
     assert lib.nerf_kabsch(16, 16, 2, 1, 16, 16, 16, None, None) == -1
     assert lib.nerf_kabsch(16, 16, 5000, 1, 16, 16, 16, None, None) == -1

@@ -21,6 +21,18 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 FAMILIES = ["gaborf", "sarf"]
+RAGGED = FAMILIES + ["garf"]          # the ragged multi-slab launch also runs GARF's Gaussian (same kernels)
+
+
+def _gauss_fwd(z, s):
+    return torch.exp((-(z * z)) * (s * s + 1e-6))
+
+
+def _gauss_bwd(g, z, s):
+    """garf/gaussian.py:8-31 and the backward of s ** 2: (dz, ds)."""
+    v = s * s + 1e-6
+    ge = g * torch.exp((-(z * z)) * v)
+    return -ge * 2 * z * v, (-ge * z * z).sum(0) * (2 * s)
 
 
 def g2d(a):
@@ -77,9 +89,10 @@ def test_activation_vs_fixture(golden, family):
 
 @functools.lru_cache(maxsize=None)
 def _ragged(family):
-    """Computed once per family, shared by the two tests below.  M = 33,281 = 65 x 512 + 1 rows:
+    """Computed once per family (Gabor, Sarf, and GARF's Gaussian through nerf_gauss_act_*), shared
+    by the two tests below.  M = 33,281 = 65 x 512 + 1 rows:
     the kernels cut them into ceil(M / 512) = 66 slabs of ceil(M / 66) = 505 rows, the last one of
-    456 (as gauss.hip does: no one-row slab is launched), which is more than 64 slabs, so the
+    456 (no one-row slab is launched), which is more than 64 slabs, so the
     reduction takes its second level with two chunks.  N = 37: one ragged column block, no multiple
     of 4.  Padded buffers (ld = 40) with NaN guard rows and columns, backward in place, two
     backward runs.  z, grad_y = randn as in GaussAct's large test;
@@ -89,7 +102,6 @@ def _ragged(family):
     from nerf_amd import kernels as K
     torch.manual_seed(12)
     M, N, LD, GR = 33_281, 37, 40, 3
-    kind = KINDS[family]
     z = torch.randn(M, N)
     gy = torch.randn(M, N)
     if family == "gaborf":
@@ -101,13 +113,21 @@ def _ragged(family):
     zb = torch.full((M + GR, LD), nan, device=DEV)
     zb[:M, :N] = z.to(DEV)
     yb = torch.full((M + GR, LD), nan, device=DEV)
-    K.param_act_fwd(kind, zb[:M], N, psd, yb[:M])
+    if family == "garf":
+        fwd = lambda z_, y_: K.gauss_act_fwd(z_, N, psd[0], y_)
+        bwd = lambda g_, z_, dz_, gr: K.gauss_act_bwd(g_, z_, N, psd[0], dz_, gr[0])
+        ref_fwd, ref_bwd = _gauss_fwd, _gauss_bwd
+    else:
+        fwd = lambda z_, y_: K.param_act_fwd(KINDS[family], z_, N, psd, y_)
+        bwd = lambda g_, z_, dz_, gr: K.param_act_bwd(KINDS[family], g_, z_, N, psd, dz_, gr)
+        ref_fwd, ref_bwd = functools.partial(act_fwd, family), functools.partial(act_bwd, family)
+    fwd(zb[:M], yb[:M])
     runs = []
     for _ in range(2):
         gb = torch.full((M + GR, LD), nan, device=DEV)
         gb[:M, :N] = gy.to(DEV)
         grads = [torch.empty(N, device=DEV) for _ in ps]
-        K.param_act_bwd(kind, gb[:M], zb[:M], N, psd, gb[:M], grads)      # grad_z == grad_y
+        bwd(gb[:M], zb[:M], gb[:M], grads)                              # grad_z == grad_y
         runs.append((gb, grads))
     for buf in (yb, runs[0][0], runs[1][0]):
         assert torch.isnan(buf[M:]).all() and torch.isnan(buf[:, N:]).all()      # guards untouched
@@ -116,8 +136,8 @@ def _ragged(family):
     for a, b in zip(runs[0][1], runs[1][1]):
         assert torch.equal(a, b)                   # fixed-order reduction: bit-identical
     z64, g64, p64 = z.double(), gy.double(), [p.double() for p in ps]
-    ref = (act_fwd(family, z64, *p64),) + tuple(act_bwd(family, g64, z64, *p64))
-    ref32 = (act_fwd(family, z, *ps),) + tuple(act_bwd(family, gy, z, *ps))
+    ref = (ref_fwd(z64, *p64),) + tuple(ref_bwd(g64, z64, *p64))
+    ref32 = (ref_fwd(z, *ps),) + tuple(ref_bwd(gy, z, *ps))
     got = (yb[:M, :N].cpu(), runs[0][0][:M, :N].cpu()) + tuple(t.cpu() for t in runs[0][1])
     return got, ref, ref32
 
@@ -135,7 +155,7 @@ def test_ragged_multi_slab_guards_determinism_and_fp32_yardstick(family):
         assert err <= bound, (n, err, bound)
 
 
-@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("family", RAGGED)
 def test_ragged_multi_slab(family):
     """The same launch against the fp64 restatement with GaussAct's large-test bounds
     (test_gpu_garf_ipe.py:119-121: y 1e-7 + 1e-6 rel, dz 1e-6 + 1e-5 rel, parameter gradients
@@ -144,8 +164,8 @@ def test_ragged_multi_slab(family):
     one fp32 ulp of the cos / sin argument (p z up to ~25, f / q up to ~8) enters y undamped.  The
     kernels therefore carry the argument's rounding error along (csrc/param_act.h, sincos_arg)."""
     got, ref, ref32 = _ragged(family)
-    names = ["y", "dz"] + [f"d_{p}" for p in PARAMS[family]]
-    tols = [(1e-7, 1e-6), (1e-6, 1e-5)] + [(1e-3, 1e-4)] * len(PARAMS[family])
+    names = ["y", "dz"] + [f"d_{p}" for p in PARAMS.get(family, ("inv_standard_deviation",))]
+    tols = [(1e-7, 1e-6), (1e-6, 1e-5)] + [(1e-3, 1e-4)] * (len(names) - 2)
     worst = []
     for n, a, b, b32, (atol, rtol) in zip(names, got, ref, ref32, tols):
         over = ((a.double() - b).abs() - (atol + rtol * b.abs())).max().item()

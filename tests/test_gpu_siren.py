@@ -1,5 +1,5 @@
 """GPU parity of SIREN's sine (csrc/param_act.hip nerf_sine_act_*, the epilogues of
-nerf_linear_sine_x3) and of LinearSine / NerfModel / NerfSiren (nerf_amd/model_siren.py) against the
+nerf_linear_sine_x3; the epilogue-against-separate-pass test also runs its siblings, the Gaussian, Gabor and Sarf) and of LinearSine / NerfModel / NerfSiren (nerf_amd/model_siren.py) against the
 reference's fixture (tests/golden/siren.npz).
 
 Bounds.  The sine alone: 2e-7 absolute on y (sincos_enc's stated ~1e-7 plus one rounding), and
@@ -123,16 +123,89 @@ def test_sine_act_empty():
     K.sine_act_bwd(z, z, 8, torch.empty(0, 8, device=DEV))
 
 
+FAMILY = ["gauss", "gabor", "sarf"]            # the sine's siblings: the activations with parameters
+
+
+def _act_params(act, n):
+    """Parameters of `act` for n channels in the reference's init ranges (inverse std / frequency in
+    [0.5, 2), spread in [0, 2 pi)), as nn.Parameters on the device."""
+    gen = torch.Generator().manual_seed(34)
+    ps = [torch.rand(n, generator=gen) * 1.5 + 0.5]
+    if act == "gabor":
+        ps.append(torch.rand(n, generator=gen) * 2 * math.pi)
+    return tuple(torch.nn.Parameter(p.to(DEV)) for p in ps)
+
+
+@pytest.mark.parametrize("act", FAMILY)
+def test_act_empty(act):
+    """M = 0 for the sine's siblings: nothing to do, and the backward (accumulate = 0) zeroes the
+    parameter gradients."""
+    lp = _layer(8, 4, act)
+    z = torch.empty(0, 8, device=DEV)
+    lp.act_fwd(z, torch.empty(0, 8, device=DEV))
+    grads = [torch.full((8,), float("nan"), device=DEV) for _ in lp.pact]
+    lp.act_bwd(z, z, torch.empty(0, 8, device=DEV), grads)
+    for g in grads:
+        assert torch.equal(g, torch.zeros(8, device=DEV))
+
+
 # --------------------------------------------------------------------- epilogue = separate passes
-def _layer(n_out, k_in):
+def _layer(n_out, k_in, act="sine"):
+    from nerf_amd._lib import NERF_ACT_GABOR, NERF_ACT_SARF
     from nerf_amd.mlp import LayerPlan, Source
     torch.manual_seed(7)
     lin = torch.nn.Linear(k_in, n_out).to(DEV)
     srcs = [Source("pos", 4, 32)] if k_in == 4 else [Source("pos", 256, 256), Source("dir", 4, 32)]
-    lp = LayerPlan(lin, srcs, False, sine=True)
+    if act == "sine":
+        lp = LayerPlan(lin, srcs, False, sine=True)
+    elif act == "gauss":
+        lp = LayerPlan(lin, srcs, False, gauss=_act_params(act, n_out)[0])
+    else:
+        lp = LayerPlan(lin, srcs, False, act=(NERF_ACT_GABOR if act == "gabor" else NERF_ACT_SARF,
+                                               _act_params(act, n_out)))
     lp.finalize(torch.device(DEV))
     lp.pack("x3")
     return lp
+
+
+def _epilogue_and_separate(lp, n_out, k_in, z_range):
+    """One layer (M = 257: one full 256-row tile and one ragged row; K = 4, one segment, or 256 + 4,
+    two) through the GEMM epilogue and through the GEMM followed by the stand-alone pass.  Asserts
+    that z, y and dz of the two routes are bitwise equal and that the parameter gradients agree up
+    to the fp64 summation order (rtol 1e-5, atol 1e-6: the bounds of
+    test_garf_gauss_epilogue_matches_separate_passes and of the Gabor / Sarf
+    test_epilogue_matches_separate_passes).  Gabor's and Sarf's backward epilogue must be refused
+    for n_out > 128; the separate pass then runs alone.  Returns (z, y, dz) of the epilogue route,
+    dz of the separate pass where the epilogue was refused."""
+    from nerf_amd import kernels as K
+    from nerf_amd._lib import NERF_EPI_BIAS
+    M = 257
+    gen = torch.Generator().manual_seed(32)
+    a_main = (torch.rand(M, 256, generator=gen) * 2 - 1).to(DEV)
+    a_tail = (torch.rand(M, 4, generator=gen) * 2 - 1).to(DEV)
+    segs = [(a_tail, 4, 1)] if k_in == 4 else [(a_main, 256, 1), (a_tail, 4, 1)]
+    bias = lp.module.bias
+    # forward
+    z1, y1, z2, y2 = (torch.empty(M, n_out, device=DEV) for _ in range(4))
+    assert lp.linear_act_x3(segs, M, lp.Wpx, lp.Kp, n_out, z1, bias=bias, y=y1)
+    K.linear_fwd_x3(segs, M, lp.Wpx, lp.Kp, n_out, bias, z2, NERF_EPI_BIAS)
+    lp.act_fwd(z2, y2)
+    assert torch.equal(z1, z2) and torch.equal(y1, y2)
+    # backward: out = act'(z) (A W^T) with a pre-activation of the layer's range
+    zpre = ((torch.rand(M, n_out, generator=gen) * 2 - 1) * z_range).to(DEV)
+    dz1, g2, dz2 = (torch.empty(M, n_out, device=DEV) for _ in range(3))
+    gr1 = [torch.full((n_out,), float("nan"), device=DEV) for _ in lp.pact]
+    gr2 = [torch.full((n_out,), float("nan"), device=DEV) for _ in lp.pact]
+    fused = lp.linear_act_x3(segs, M, lp.Wpx, lp.Kp, n_out, dz1, z=zpre, grads=gr1)
+    assert fused == (lp.act is None or n_out <= 128)
+    K.linear_fwd_x3(segs, M, lp.Wpx, lp.Kp, n_out, None, g2, 0)
+    lp.act_bwd(g2, zpre, dz2, gr2)
+    assert dz2.abs().max().item() > 0 and all(torch.isfinite(g).all() for g in gr2)
+    if fused:
+        assert torch.equal(dz1, dz2)
+        for a, b in zip(gr1, gr2):
+            torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6)
+    return z1, y1, dz1 if fused else dz2
 
 
 @pytest.mark.parametrize("k_in", [4, 260])
@@ -143,30 +216,19 @@ def test_epilogue_equals_separate_passes(n_out, k_in):
     full 256-row tile and one ragged row; K = 4 (one segment) and 256 + 4 (two).  The 256-column
     backward epilogue shipped (no scratch, no spills), so it is tested like the 128-column one;
     N = 260 takes two column blocks (256 + 4) in both modes."""
-    from nerf_amd import kernels as K
-    from nerf_amd._lib import NERF_EPI_BIAS
-    M = 257
-    lp = _layer(n_out, k_in)
-    gen = torch.Generator().manual_seed(32)
-    a_main = (torch.rand(M, 256, generator=gen) * 2 - 1).to(DEV)
-    a_tail = (torch.rand(M, 4, generator=gen) * 2 - 1).to(DEV)
-    segs = [(a_tail, 4, 1)] if k_in == 4 else [(a_main, 256, 1), (a_tail, 4, 1)]
-    bias = lp.module.bias
-    # forward
-    z1, y1, z2, y2 = (torch.empty(M, n_out, device=DEV) for _ in range(4))
-    assert K.linear_sine_x3(segs, M, lp.Wpx, lp.Kp, n_out, z1, bias=bias, y=y1)
-    K.linear_fwd_x3(segs, M, lp.Wpx, lp.Kp, n_out, bias, z2, NERF_EPI_BIAS)
-    K.sine_act_fwd(z2, n_out, y2)
-    assert torch.equal(z1, z2) and torch.equal(y1, y2)
+    z1, y1, dz1 = _epilogue_and_separate(_layer(n_out, k_in), n_out, k_in, 30.0)
     assert (y1 - torch.sin(z1.double()).float()).abs().max().item() <= 2e-7
-    # backward: out = (A W^T) * cos(z) with a pre-activation of a SIREN layer's range
-    zpre = ((torch.rand(M, n_out, generator=gen) * 60 - 30)).to(DEV)
-    dz1, g2, dz2 = (torch.empty(M, n_out, device=DEV) for _ in range(3))
-    assert K.linear_sine_x3(segs, M, lp.Wpx, lp.Kp, n_out, dz1, z=zpre)
-    K.linear_fwd_x3(segs, M, lp.Wpx, lp.Kp, n_out, None, g2, 0)
-    K.sine_act_bwd(g2, zpre, n_out, dz2)
-    assert torch.equal(dz1, dz2)
     assert dz1.abs().max().item() > 0
+
+
+@pytest.mark.parametrize("k_in", [4, 260])
+@pytest.mark.parametrize("n_out", [128, 256, 260])
+@pytest.mark.parametrize("act", FAMILY)
+def test_epilogue_equals_separate_passes_family(act, n_out, k_in):
+    """The same for the Gaussian (nerf_linear_gauss_x3 against nerf_gauss_act_*) and for Gabor and
+    Sarf (nerf_linear_act_x3 against nerf_param_act_*), whose backward epilogue exists for
+    N <= 128 only: at 256 and 260 it must be refused."""
+    _epilogue_and_separate(_layer(n_out, k_in, act), n_out, k_in, 2.0)
 
 
 def _model_run(m, pos, d, w):
