@@ -954,6 +954,56 @@ int nerf_composite_packed_bwd(const float* sigma, int64_t sigma_stride, const fl
                               float* grad_sigma, int64_t gs_stride, float* grad_rgb, int64_t gc_stride,
                               void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Sample points of packed samples: the step between the marching and the field.
+ *
+ * The points contract, every operation rounded to fp32 separately (no contraction), for sample i of
+ * ray r = ray_indices[i] (int64 [n_samples]; rays_o, rays_d [n_rays][3]):
+ *   1. tm = (t_starts_i + t_ends_i) * 0.5f;
+ *   2. positions_i[a] = rays_o[r][a] + tm * rays_d[r][a], a = 0, 1, 2 (row stride pos_stride >= 3;
+ *      columns 3.. of a row are not touched);
+ *   3. dirs_i[a] = rays_d[r][a] (row stride dirs_stride >= 3; dirs NULL: skipped);
+ *   4. r outside [0, n_rays): the rows are NaN and nothing is read out of range (the convention of
+ *      nerf_pose_rays_fwd).
+ * Steps 1-2 are steps 8-9 of the marching contract, so a kept sample is evaluated bitwise at the
+ * point whose grid cell was tested.  One thread per sample; no store at or past row n_samples.
+ * nerf_packed_points_bwd: seg [n_rays + 1] int64 (ray r owns samples [seg[r], seg[r+1]),
+ * non-decreasing, clamped to [0, n_samples] by the kernel), g_positions (row stride gp_stride >= 3)
+ * and optionally g_dirs (row stride gd_stride >= 3, NULL = zero) to
+ *   g_o[r] = sum_i g_positions_i,  g_d[r] = sum_i (tm_i * g_positions_i + g_dirs_i)   [n_rays][3]
+ * over the ray's segment, both overwritten, zeros for an empty ray.  One wave per ray, fixed-order
+ * fp64 sums rounded once to fp32, no atomics: bitwise reproducible.  No gradient reaches t_starts /
+ * t_ends (the sampler is not differentiated, as in nerfacc).
+ * Both: n_rays == 0 or n_samples == 0: NERF_OK without a launch (nothing is written, so the caller
+ * zeroes g_o / g_d itself); null or misaligned pointers, a stride below 3: NERF_ERR_INVALID_ARG
+ * before any launch.
+ * ------------------------------------------------------------------------- */
+int nerf_packed_points_fwd(const float* rays_o, const float* rays_d, int64_t n_rays, const int64_t* ray_indices,
+                           const float* t_starts, const float* t_ends, int64_t n_samples, float* positions,
+                           int64_t pos_stride, float* dirs, int64_t dirs_stride, void* stream);
+int nerf_packed_points_bwd(const int64_t* seg, int64_t n_rays, const float* t_starts, const float* t_ends,
+                           int64_t n_samples, const float* g_positions, int64_t gp_stride, const float* g_dirs,
+                           int64_t gd_stride, float* g_o, float* g_d, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Distortion loss of mip-NeRF 360 (nerfacc.distortion restated, parity unpinned) on packed samples:
+ * ray r owns samples [seg[r], seg[r+1]) of weights, t_starts, t_ends (fp32 [n_samples]; seg as above).
+ * With m_i = (t_starts_i + t_ends_i) / 2 and delta_i = t_ends_i - t_starts_i formed in fp64, and
+ * W_<i, WM_<i (W_>i, WM_>i) the fp64 sums of w and w * m over the ray's earlier (later) samples:
+ *   loss[r]         = fp32( sum_i [ w_i^2 delta_i / 3 + 2 w_i (m_i W_<i - WM_<i) ] )        [n_rays]
+ *   grad_weights[i] = fp32( g_loss[r] [ 2/3 w_i delta_i + 2 (m_i W_<i - WM_<i + WM_>i - m_i W_>i) ] )
+ * That is sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 delta_i when the midpoints ascend along the
+ * ray: the contract, not checked (marched samples and proposal intervals satisfy it).
+ * One wave per ray, fp64 wave scans and running totals across 64-sample chunks, no atomics:
+ * deterministic.  An empty ray gets loss 0 and no gradient store.
+ * n_rays == 0 or n_samples == 0: NERF_OK without a launch (the caller zeroes loss itself); null or
+ * misaligned pointers: NERF_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------- */
+int nerf_distortion_fwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* seg,
+                        int64_t n_rays, int64_t n_samples, float* loss, void* stream);
+int nerf_distortion_bwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* seg,
+                        int64_t n_rays, int64_t n_samples, const float* g_loss, float* grad_weights, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

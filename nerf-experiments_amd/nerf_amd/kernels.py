@@ -1296,3 +1296,114 @@ def composite_packed_bwd(sigma, rgb, t_starts, t_ends, seg, weights, trans, g_co
         end.record()
     _lib.check(st, "nerf_composite_packed_bwd")
     return d_sigma, d_rgb
+
+
+# ----------------------------------------------------------------------------- packed sample points
+def _flat_samples(pairs, n: int | None = None) -> int:
+    for name, t in pairs:
+        _require_cuda_f32(name, t)
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [n_samples] tensor")
+        n = t.shape[0] if n is None else n
+        if t.shape[0] != n:
+            raise ValueError(f"{name} must have one entry per sample")
+    return n
+
+
+def _check_seg(seg: torch.Tensor, device) -> int:
+    if seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1 or not seg.is_contiguous() \
+            or seg.device != device:
+        raise ValueError("seg must be a contiguous int64 [n_rays + 1] tensor on the samples' device")
+    return seg.numel() - 1
+
+
+def packed_points_fwd(rays_o: torch.Tensor, rays_d: torch.Tensor, ray_indices: torch.Tensor, t_starts: torch.Tensor,
+                      t_ends: torch.Tensor, want_dirs: bool = True):
+    """nerf_packed_points_fwd: (positions [N, 3], dirs [N, 3] or None) of the samples' midpoints, each
+    operation rounded to fp32 alone (the marching contract's points)."""
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        _require_cuda_f32(name, t)
+        if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [n_rays, 3] tensor")
+    if rays_d.shape != rays_o.shape:
+        raise ValueError("rays_o and rays_d must share their shape")
+    n = _flat_samples((("t_starts", t_starts), ("t_ends", t_ends)))
+    if ray_indices.dtype != torch.int64 or tuple(ray_indices.shape) != (n,) or not ray_indices.is_contiguous() \
+            or ray_indices.device != rays_o.device:
+        raise ValueError("ray_indices must be a contiguous int64 [n_samples] tensor on the rays' device")
+    R = rays_o.shape[0]
+    f = dict(device=rays_o.device, dtype=torch.float32)
+    pos = torch.empty(n, 3, **f) if R else torch.full((n, 3), float("nan"), **f)
+    dirs = (torch.empty(n, 3, **f) if R else torch.full((n, 3), float("nan"), **f)) if want_dirs else None
+    # algorithmic bytes: index, t_starts, t_ends in, positions (+ dirs) out per sample; the rays once
+    end = TIMER.bracket("packed_points_fwd", nbytes=n * (28 + (12 if want_dirs else 0)) + 24 * R,
+                        fn="packed_points_fwd_kernel") if TIMER is not None else None
+    st = _lib.load().nerf_packed_points_fwd(_ptr(rays_o), _ptr(rays_d), R, _ptr(ray_indices), _ptr(t_starts),
+                                            _ptr(t_ends), n, _ptr(pos), 3, _ptr(dirs), 3, _stream(rays_o.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_packed_points_fwd")
+    return pos, dirs
+
+
+def packed_points_bwd(seg: torch.Tensor, t_starts: torch.Tensor, t_ends: torch.Tensor, g_positions: torch.Tensor,
+                      g_dirs: torch.Tensor | None = None):
+    """nerf_packed_points_bwd: (g_o [R, 3], g_d [R, 3]), fixed-order fp64 segment sums."""
+    n = _flat_samples((("t_starts", t_starts), ("t_ends", t_ends)))
+    R = _check_seg(seg, t_starts.device)
+    for name, g in (("g_positions", g_positions), ("g_dirs", g_dirs)):
+        if g is None and name == "g_dirs":
+            continue
+        _require_cuda_f32(name, g)
+        if tuple(g.shape) != (n, 3) or not g.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [n_samples, 3] tensor")
+    f = dict(device=t_starts.device, dtype=torch.float32)
+    if n == 0:
+        return torch.zeros(R, 3, **f), torch.zeros(R, 3, **f)
+    g_o, g_d = torch.empty(R, 3, **f), torch.empty(R, 3, **f)
+    end = TIMER.bracket("packed_points_bwd", nbytes=n * (20 + (12 if g_dirs is not None else 0)) + 32 * R,
+                        fn="packed_points_bwd_kernel") if TIMER is not None else None
+    st = _lib.load().nerf_packed_points_bwd(_ptr(seg), R, _ptr(t_starts), _ptr(t_ends), n, _ptr(g_positions), 3,
+                                            _ptr(g_dirs), 3, _ptr(g_o), _ptr(g_d), _stream(t_starts.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_packed_points_bwd")
+    return g_o, g_d
+
+
+# ----------------------------------------------------------------------------- distortion loss
+def distortion_fwd(weights: torch.Tensor, t_starts: torch.Tensor, t_ends: torch.Tensor, seg: torch.Tensor) -> torch.Tensor:
+    """nerf_distortion_fwd: loss [R] of the rays owning samples [seg[r], seg[r+1])."""
+    n = _flat_samples((("weights", weights), ("t_starts", t_starts), ("t_ends", t_ends)))
+    R = _check_seg(seg, weights.device)
+    if n == 0:
+        return torch.zeros(R, device=weights.device, dtype=torch.float32)
+    loss = torch.empty(R, device=weights.device, dtype=torch.float32)
+    end = TIMER.bracket("distortion_fwd", nbytes=12 * n + 12 * R, fn="distortion_fwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_distortion_fwd(_ptr(weights), _ptr(t_starts), _ptr(t_ends), _ptr(seg), R, n, _ptr(loss),
+                                         _stream(weights.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_distortion_fwd")
+    return loss
+
+
+def distortion_bwd(weights: torch.Tensor, t_starts: torch.Tensor, t_ends: torch.Tensor, seg: torch.Tensor,
+                   g_loss: torch.Tensor) -> torch.Tensor:
+    """nerf_distortion_bwd: d weights [N] of <g_loss, loss>."""
+    n = _flat_samples((("weights", weights), ("t_starts", t_starts), ("t_ends", t_ends)))
+    R = _check_seg(seg, weights.device)
+    _require_cuda_f32("g_loss", g_loss)
+    if tuple(g_loss.shape) != (R,) or not g_loss.is_contiguous():
+        raise ValueError("g_loss must be a contiguous [n_rays] tensor")
+    grad = torch.empty_like(weights)
+    # the segment is walked twice (totals, then gradients): 12 bytes in per walk, 4 out
+    end = TIMER.bracket("distortion_bwd", nbytes=28 * n + 12 * R, fn="distortion_bwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_distortion_bwd(_ptr(weights), _ptr(t_starts), _ptr(t_ends), _ptr(seg), R, n, _ptr(g_loss),
+                                         _ptr(grad), _stream(weights.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_distortion_bwd")
+    return grad
