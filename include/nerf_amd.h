@@ -145,7 +145,9 @@ int nerf_resample_pdf(const float* t_coarse, const float* weights, const float* 
  *                 "left") or (t_start[n]+t_end[n])/2 (query=1, "middle").
  * kind 0 = Fourier / BARF: args = p_d * (scale * 2^k) (fp32), out =
  *   [p (if identity) | mask_k*cos(args) (d-major, k-minor) | mask_k*sin(args)].
- *   use_mask == 0 means all ones (plain FourierFeatures).  levels <= 16.
+ *   use_mask == 0 means all ones (plain FourierFeatures).  levels <= 16.  cos / sin of an fp32
+ *   argument: within 1e-7 (fast path) for |args| < 2^19, libm sincosf from 2^19 on (scale 2 pi at
+ *   16 levels reaches that at |p| = 2.5); +-inf and NaN give NaN.
  * kind 1 = integrated (mip-NeRF IPE, positional_encodings.py:170-240); needs
  *   dir (per ray, or the direction itself when x != NULL via xdir),
  *   pixel_width (pw_mode 0: pw[ray]; 1: pw[n % n_rays] — the reference's

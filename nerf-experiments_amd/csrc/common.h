@@ -123,16 +123,24 @@ __device__ __forceinline__ float softplus_thr8_grad(float x) {
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---------------------------------------------------------------------------
-// sin and cos of one fp32 argument for the encodings (|x| up to scale * 2^15 * |p|):
+// sin and cos of one fp32 argument, shared by the encodings, the Gabor / Sarf activations and
+// SIREN's sine.  Fast path, |x| < kSincosFastMax = 2^19:
 // k = rint(x * 2/pi); r = x - k * pi/2 by a three-term fp32 Cody-Waite reduction with fused
-// multiply-adds (each k * c_i exact inside its FMA: |r| error ~1e-7 for |k| < 2^24), then fp32
-// minimax polynomials on [-pi/4, pi/4] (Cephes sinf/cosf, ~1 ulp) and the quadrant swap.  About
-// a third of the instructions of the libm sincosf, within ~1e-7 absolute of the correctly
-// rounded values; larger or non-finite arguments take sincosf.  (-DNERF_SINCOS_FP64_REDUCTION:
-// the same with a two-term fp64 reduction, measured 2 % slower in the encoding kernel.)
+// multiply-adds (each k * c_i exact inside its FMA), then fp32 minimax polynomials on
+// [-pi/4, pi/4] (Cephes sinf/cosf, ~1 ulp) and the quadrant swap.  About a third of the
+// instructions of the libm sincosf.  Swept on the host build of this source over every fp32
+// value of [2^12, 2^19) and every 61st below (tests/test_sincos_host.py), exhaustively:
+// 9.5e-8 absolute for |x| < 2^19, sin(-x) = -sin(x) and cos(-x) = cos(x) bit for bit.  The
+// limit is where the fp32 product x * 2/pi still rounds to the right k: from 2^20 on its
+// rounding moves k off by one, r leaves [-pi/4, pi/4] and the error grows past 1e-7 (3.7e-7 in
+// [2^20, 2^21), unbounded above 2^25).  Everything else, |x| >= 2^19, +-inf and NaN, takes
+// sincosf.  (-DNERF_SINCOS_FP64_REDUCTION: the same with a two-term fp64 reduction, measured
+// 2 % slower in the encoding kernel; the same limit, since k is formed the same way.)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void sincos_enc(float x, float* s, float* c) {
-    if (!(fabsf(x) < 1073741824.0f)) {
+constexpr float kSincosFastMax = 524288.0f;     // 2^19
+
+__host__ __device__ __forceinline__ void sincos_enc(float x, float* s, float* c) {
+    if (!(fabsf(x) < kSincosFastMax)) {
         sincosf(x, s, c);
         return;
     }

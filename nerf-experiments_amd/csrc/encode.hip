@@ -13,8 +13,9 @@
 // read).  Rows of <= 128 columns go through encode_fwd_lds_kernel: 64 samples per block,
 // positions computed once per sample, ONE sin/cos evaluation per (sample, d, k) feeding both
 // the cos and the sin column, the row image staged in LDS and written with coalesced 16-byte
-// stores.  sin/cos use sincos_enc (fp64 Cody-Waite reduction + fp32 minimax, ~1e-7 abs) —
-// libm sincosf made the kernel VALU-bound.  Wider / unaligned rows: one thread per 4 columns.
+// stores.  sin/cos use sincos_enc (fp32 Cody-Waite reduction + fp32 minimax, 9.5e-8 abs, for
+// arguments below 2^19; sincosf from there on) — libm sincosf for every argument made the kernel
+// VALU-bound.  Wider / unaligned rows: one thread per 4 columns.
 // Floating-point contraction is off so every other fp32 operation rounds exactly where the
 // reference's does.
 #include <stddef.h>

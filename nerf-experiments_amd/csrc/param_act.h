@@ -25,10 +25,11 @@
 // finite there).  sin / cos through sincos_enc (common.h), exp through expf, IEEE divisions.
 //
 // The sin / cos argument carries its rounding error along (sincos_arg): one fp32 ulp of p z (up to
-// ~25) or of f / q (up to ~8) is 5e-7 .. 2e-6, and it enters y undamped, where the Gaussian has a
-// single exp whose argument error is relative to y.  Gabor takes the exact product p z as
-// hi + lo (one FMA); Sarf forms t, q and f / q in fp64 and splits the quotient.  Everything else
-// is fp32 arithmetic in the order written above.
+// ~25 near initialisation) or of f / q (up to ~8) is 5e-7 .. 2e-6, and it enters y undamped, where
+// the Gaussian has a single exp whose argument error is relative to y.  Gabor takes the exact
+// product p z as hi + lo (one FMA); Sarf forms t, q and f / q in fp64 and splits the quotient.
+// Arguments of 4096 and more (a grown spread or frequency) are wrapped into [-pi, pi] in fp64
+// first.  Everything else is fp32 arithmetic in the order written above.
 //
 // kChain: the first parameter is s of v = s^2 + 1e-6, so its column sum (dv) is finished with the
 // chain-rule factor 2 s (param_reduce).
@@ -37,13 +38,55 @@
 
 namespace nerf {
 
-// sin and cos of hi + lo, |lo| <= ulp(hi) / 2: sincos_enc(hi) and the first-order term in lo
-// (the second-order term is below 1e-12).
-__device__ __forceinline__ void sincos_arg(float hi, float lo, float* s, float* c) {
+// sin and cos of hi + lo, |lo| <= 2^-13: sincos_enc(hi) and the first-order term in lo (the
+// second-order term lo^2 / 2 is below 7.5e-9).
+__host__ __device__ __forceinline__ void sincos_hi_lo(float hi, float lo, float* s, float* c) {
     float s0, c0;
     sincos_enc(hi, &s0, &c0);
     *s = __builtin_fmaf(c0, lo, s0);
     *c = __builtin_fmaf(-s0, lo, c0);
+}
+
+// Arguments of 4096 and more.  Below, |lo| <= ulp(hi) / 2 <= 2^-13 and sincos_hi_lo serves as it
+// is (every argument of a network near its initialisation).  A spread or a frequency that has
+// grown takes the argument further (p z without limit, f / q up to f^3), where lo is no longer
+// small (0.03 at 2^19, 128 at 2^31) and a first-order term in it is simply wrong.  There the
+// argument, exact in fp64, is first taken into [-pi, pi]: a - k 2pi with k = rint(a / 2pi) and
+// 2pi in two fp64 terms under fused multiply-adds (k 2pi_hi exact inside its FMA, the second
+// term's error below 1e-20 for |a| < 2^40), and the remainder is split into hi + lo again.
+// wrap_2pi returns false for |a| >= 2^40 and for non-finite a: the caller then takes sincos_enc
+// of the fp32 argument alone (sincosf: NaN for +-inf and NaN).
+constexpr float kSincosArgMax = 4096.0f;
+
+__host__ __device__ __forceinline__ bool wrap_2pi(double* a) {
+    if (!(fabs(*a) < 1099511627776.0)) return false;
+    const double k = rint(*a * 0.15915494309189535);
+    double r = __builtin_fma(k, -6.283185307179586, *a);
+    r = __builtin_fma(k, -2.4492935982947064e-16, r);
+    *a = r;
+    return true;
+}
+
+// sin and cos of hi + lo, |lo| <= ulp(hi) / 2 (hi + lo an exact product or quotient)
+__host__ __device__ __forceinline__ void sincos_arg(float hi, float lo, float* s, float* c) {
+    if (!(fabsf(hi) < kSincosArgMax)) {
+        double a = (double)hi + (double)lo;
+        if (wrap_2pi(&a)) {
+            hi = (float)a;
+            lo = (float)(a - (double)hi);
+        } else {
+            lo = 0.0f;
+        }
+    }
+    sincos_hi_lo(hi, lo, s, c);
+}
+
+// the same of an fp64 argument
+__host__ __device__ __forceinline__ void sincos_arg(double a, float* s, float* c) {
+    bool split = true;
+    if (!(fabs(a) < (double)kSincosArgMax)) split = wrap_2pi(&a);
+    const float hi = (float)a;
+    sincos_hi_lo(hi, split ? (float)(a - (double)hi) : 0.0f, s, c);
 }
 
 // GARF's Gaussian.  kKind is the tile GEMM's template value 0; no public `kind` takes it.
@@ -115,8 +158,7 @@ struct SarfFn {
 #pragma clang fp contract(off)
         const double td = (double)fabsf(z) + 1e-4;
         const double ad = (double)k.f / (td * td + k.rd);
-        const float a = (float)ad;
-        sincos_arg(a, (float)(ad - (double)a), s, c);
+        sincos_arg(ad, s, c);
     }
     static __device__ __forceinline__ float fwd(float z, P k) {
 #pragma clang fp contract(off)

@@ -8,7 +8,8 @@ BITWISE: the rows it stores for the weight gradients equal nerf_encode_fwd's, an
 layer output and gradient of a render_raw step is bitwise that of the unfused step.  Encoders: the
 C3 mip workload's masked integrated encoding (pixel width as 800^2 / per-sample, sigma 0 and the
 > 0.25 branch, distributed and per-axis variance), BARF's masked Fourier features at a fractional
-alpha, plain Fourier features (n2v) and 3d-ingp's scale-1 features as the direction encoder;
+alpha, plain Fourier features (n2v; n2v_far with arguments on both sides of sincos_enc's fast-path
+limit) and 3d-ingp's scale-1 features as the direction encoder;
 BASELINE's 4096 x 64 batch and ragged ray x sample counts (M not a multiple of the 128-sample
 workgroup tile), query at the interval start and midpoint."""
 import math
@@ -47,7 +48,7 @@ def _model(kind):
     elif kind == "barf":
         pos = BarfPositionalEncoding(10, 3.7, 0, 1, True, 1.0)       # fractional alpha: a ramped level
         dirs = BarfPositionalEncoding(4, 1.5, 0, 1, True, 1.0)
-    elif kind == "n2v":
+    elif kind in ("n2v", "n2v_far"):
         pos = FourierFeatures(10, 2 * math.pi)
         dirs = FourierFeatures(4, 1.0)
     else:                                               # 3d-ingp's direction features
@@ -75,11 +76,18 @@ def _encode(model, o, d, t0, t1, pw, S, query, pw_mode, defer):
 
 @pytest.mark.parametrize("kind,n_rays,S,query,pw_mode", [
     ("mip", 4096, 64, 1, 0), ("mip", 37, 65, 1, 2), ("ipe_axis", 300, 17, 1, 1), ("barf", 4096, 64, 0, 0),
-    ("barf", 129, 3, 1, 0), ("n2v", 1000, 7, 0, 0), ("ingp_dirs", 64, 64, 0, 0)])
+    ("barf", 129, 3, 1, 0), ("n2v", 1000, 7, 0, 0), ("ingp_dirs", 64, 64, 0, 0), ("n2v_far", 129, 3, 1, 0)])
 def test_generated_encodings_bitwise(kind, n_rays, S, query, pw_mode):
+    """n2v_far: the origins taken 100 times further out, positions up to +-290, so that the arguments of
+    the upper levels (2 pi 2^9 x 250 = 8e5) lie past sincos_enc's fast-path limit 2^19 (common.h) and those
+    of the lower ones below it: the in-kernel encoding takes the sincosf path bit for bit as the
+    stand-alone kernel does.  (A 16-level encoder is not generated in-kernel: its rows exceed the
+    kernel's 64-column LDS row, and mlp_fused.eligible refuses the plan from 11 levels on.)"""
     from nerf_amd import kernels as K, mlp_fused
     model = _model(kind)
     o, d, t0, t1, pw = _rays(n_rays, S)
+    if kind == "n2v_far":
+        o = o * 100.0
     if pw_mode == 2:
         pw = pw[:, None].expand(n_rays, S).contiguous()
     M = n_rays * S
