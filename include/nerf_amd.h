@@ -178,7 +178,9 @@ int nerf_encode_fwd(const nerf_pe_params* params,
 
 /* Backward of kind-0 encodings w.r.t. an explicit position input x:
  *   dx[n,d] = g_id + sum_k mask_k*scale*2^k*(-g_cos*sin(a) + g_sin*cos(a)).
- * grad_out has row stride g_ld. If accumulate, dx += ... */
+ * grad_out has row stride g_ld. If accumulate, dx += ...
+ * The three backward entry points refuse, as the forward does, an encoding of no columns
+ * (0 levels without identity): NERF_ERR_INVALID_ARG before any launch. */
 int nerf_encode_bwd(const nerf_pe_params* params, const float* x,
                     const float* grad_out, int64_t g_ld, int64_t n_samples,
                     float* dx, int32_t accumulate, void* stream);

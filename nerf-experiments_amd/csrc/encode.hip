@@ -450,6 +450,7 @@ extern "C" int nerf_encode_bwd(const nerf_pe_params* params, const float* x, con
     NERF_REQUIRE(params && x && grad_out && dx && n_samples >= 0);
     if (n_samples == 0) return NERF_OK;
     if (params->kind != 0) return NERF_ERR_UNSUPPORTED;
+    NERF_REQUIRE(params->levels >= 0 && params->levels <= 16 && out_dim_of(*params) > 0);
     NERF_REQUIRE(g_ld >= out_dim_of(*params));
     const int64_t total = n_samples * 3;
     hipLaunchKernelGGL(encode_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream),
@@ -466,7 +467,7 @@ extern "C" int nerf_encode_bwd_integrated(const nerf_pe_params* params, const fl
     if (n_samples == 0) return NERF_OK;
     NERF_REQUIRE(params->kind == 1 && params->levels >= 0 && params->levels <= 16);
     NERF_REQUIRE(x && xdir && t_start && t_end && pixel_width && grad_out && (dx || ddir));
-    NERF_REQUIRE(g_ld >= out_dim_of(*params));
+    NERF_REQUIRE(g_ld >= out_dim_of(*params) && out_dim_of(*params) > 0);
     hipLaunchKernelGGL(encode_bwd_integrated_kernel, dim3((unsigned)((n_samples + 255) / 256)), dim3(256), 0,
                        as_stream(stream), *params, x, xdir, t_start, t_end, pixel_width, grad_out, g_ld, n_samples,
                        dx, ddir, accumulate);
@@ -483,7 +484,7 @@ extern "C" int nerf_encode_bwd_rays(const nerf_pe_params* params, const float* r
     const nerf_pe_params& p = *params;
     NERF_REQUIRE(p.levels >= 0 && p.levels <= 16 && (p.kind == 0 || p.kind == 1));
     NERF_REQUIRE(ray_o && ray_d && t_start && grad_out && (d_origs || d_dirs));
-    NERF_REQUIRE(g_ld >= out_dim_of(p) && out_dim_of(p) <= 128);
+    NERF_REQUIRE(g_ld >= out_dim_of(p) && out_dim_of(p) > 0 && out_dim_of(p) <= 128);
     if (p.query != 0 || p.kind == 1) NERF_REQUIRE(t_end != nullptr);
     if (p.kind == 1) NERF_REQUIRE(pixel_width != nullptr && p.pw_mode >= 0 && p.pw_mode <= 2);
     const int64_t n = n_rays * (int64_t)samples_per_ray;
