@@ -932,6 +932,66 @@ int nerf_occ_march_write(int64_t n_rays, float step_size, int32_t mask_words, co
                          int64_t* ray_indices, float* t_starts, float* t_ends, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Cascaded occupancy-grid marching for unbounded scenes: nerfacc's OccGridEstimator(levels=L)
+ * .sampling(cone_angle=..., t_min=..., t_max=...) restated, again with a contract of our own (parity
+ * unpinned).  `levels` (1..NERF_OCC_MAX_LEVELS) nested boxes share one resolution; the host computes
+ * them (nerfacc's enlargement, in fp32: c = (lo + hi) * 0.5, h = (hi - lo) * 0.5, lo_l = c - h * 2^l,
+ * hi_l = c + h * 2^l) and passes them by value, the kernel derives nothing.
+ *
+ * Grid: aabbs = host float [levels][6], per level [xmin, ymin, zmin, xmax, ymax, zmax] (lo < hi per
+ * axis; box[l] = (lo_l, hi_l) below), resolution = host [rx, ry, rz] (1..4096 each, cells = rx * ry *
+ * rz at most 2^31), grid_bits = device uint32 words over levels * cells cells, bit (i & 31) of word
+ * i >> 5 set iff cell i = l * cells + (cx * ry + cy) * rz + cz is occupied (the flat packing of a
+ * [levels, rx, ry, rz] array).  t_lo, t_hi = device fp32 [n_rays] per-ray bounds, each optional
+ * (NULL: absent).  cone_angle >= 0.
+ *
+ * The cascaded marching contract, every operation rounded to fp32 separately (no contraction),
+ * division correctly rounded, max and min the comparisons as written:
+ *   1. steps 1-3 of the one-level contract (the slab test) against the outermost box,
+ *      box[levels - 1];
+ *   2. t_min = near > tn ? near : tn; with t_lo, t_min = t_lo[r] > t_min ? t_lo[r] : t_min;
+ *      t_max = far < tf ? far : tf; with t_hi, t_max = t_hi[r] < t_max ? t_hi[r] : t_max;
+ *   3. the ray has samples only if t_min < t_max;
+ *   4. stratified: t_min = t_min + U[ray] * dt, the Philox draw of the one-level contract;
+ *   5. step rule, cone == 0: the lattice of the one-level contract, steps 7-8:
+ *      n = min(ceilf((t_max - t_min) / dt), NERF_OCC_MAX_STEPS), t0 = t_min + (float)k * dt,
+ *      e1 = t_min + (float)(k + 1) * dt;
+ *   6. step rule, cone > 0: the recurrence s_0 = t_min, w_k = s_k * cone, h_k = w_k > dt ? w_k : dt,
+ *      s_{k+1} = s_k + h_k; step k exists iff s_k < t_max and k < NERF_OCC_MAX_STEPS; t0 = s_k,
+ *      e1 = s_{k+1}; if s_8192 < t_max the ray was cut and bit 0 of *status is set;
+ *   7. both rules: t1 = e1 < t_max ? e1 : t_max; the step is dropped unless t0 < t1;
+ *   8. tm = (t0 + t1) * 0.5, p_a = o_a + tm * d_a;
+ *   9. the step's level is the smallest l with lo_l[a] <= p_a < hi_l[a] on all three axes; with
+ *      none the step is dropped;
+ *  10. c_a = floorf(((p_a - lo_l[a]) / (hi_l[a] - lo_l[a])) * (float)res_a); kept iff 0 <= c_a <
+ *      res_a on every axis and bit l * cells + (c_x * ry + c_y) * rz + c_z is set (the grid is read
+ *      only after that range test);
+ *  11. mask capacity: the lattice as in the one-level contract (n > 64 * mask_words is cut there and
+ *      sets bit 1); the recurrence stops after min(NERF_OCC_MAX_STEPS, 64 * mask_words) steps, and
+ *      one that stops with s < t_max sets bit 0 if it stopped at NERF_OCC_MAX_STEPS, bit 1
+ *      otherwise.  h_k >= dt, so the mask_words that bound a lattice of step dt bound the recurrence;
+ *  12. consecutive kept steps of a ray abut bitwise under both rules.
+ * With levels == 1, cone == 0 and no ray bounds this is the one-level contract, and the outputs are
+ * those of nerf_occ_march_count / nerf_occ_march_write bit for bit.
+ *
+ * The two passes, the workspace (nerf_occ_march_workspace(n_rays, mask_words) bytes, the same
+ * layout), offsets_incl, the store guards and the status codes are those of the one-level pair;
+ * levels outside 1..NERF_OCC_MAX_LEVELS, a negative, infinite or NaN cone_angle, a bad box of any level:
+ * NERF_ERR_INVALID_ARG.  nerf_occ_cascade_write takes the step_size and cone_angle of the count: with
+ * cone > 0 it reruns the recurrence from the stored t_min (the same bits) and never tests the grid.
+ * One wave per ray: with cone > 0 every lane runs the chain of its chunk's 64 steps and keeps its own.
+ * ------------------------------------------------------------------------- */
+#define NERF_OCC_MAX_LEVELS 8
+int nerf_occ_cascade_count(const float* rays_o, const float* rays_d, int64_t n_rays, const float* aabbs,
+                           int32_t levels, const int32_t* resolution, const uint32_t* grid_bits, const float* t_lo,
+                           const float* t_hi, float near_plane, float far_plane, float step_size, float cone_angle,
+                           int32_t stratified, uint64_t seed, uint64_t counter, int32_t mask_words, void* workspace,
+                           size_t workspace_bytes, int32_t* status, void* stream);
+int nerf_occ_cascade_write(int64_t n_rays, float step_size, float cone_angle, int32_t mask_words,
+                           const void* workspace, size_t workspace_bytes, const int64_t* offsets_incl,
+                           int64_t n_samples, int64_t* ray_indices, float* t_starts, float* t_ends, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Compositing of packed samples: ray r owns samples [seg[r], seg[r+1]) of the flat arrays (seg
  * [n_rays + 1] int64, non-decreasing, clamped to [0, n_samples] by the kernels).  The arithmetic of
  * nerf_composite_fwd with scale 1 and act 0 on segments of any length:

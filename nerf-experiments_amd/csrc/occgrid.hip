@@ -10,36 +10,16 @@
 // the grid again, so the two passes cannot disagree on what is kept.  Every loop is bounded by
 // n <= 64 * mask_words <= NERF_OCC_MAX_STEPS, every grid read follows the cell's range test, every
 // store is guarded by the output's length.  No atomics except the OR into the status word, no LDS.
-#include "common.h"
+#include "occgrid_common.h"
 
 using namespace nerf;
 
 namespace {
 
-constexpr int kMaxWords = NERF_OCC_MAX_STEPS / NERF_WAVE;
-
 struct OccGrid {
     float lo[3], hi[3];
     int res[3];
 };
-
-// workspace: [counts int64 x n][t_min f32 x n][t_max f32 x n][n_steps i32 x n] pad to 256 [masks u64 x n x words]
-struct OccWorkspace {
-    int64_t* counts; float* tmin; float* tmax; int32_t* nsteps; unsigned long long* masks;
-};
-
-size_t header_bytes(int64_t n_rays) { return ((size_t)n_rays * 20 + 255) & ~(size_t)255; }
-
-OccWorkspace carve(void* ws, int64_t n_rays) {
-    char* p = static_cast<char*>(ws);
-    OccWorkspace w;
-    w.counts = reinterpret_cast<int64_t*>(p);
-    w.tmin = reinterpret_cast<float*>(p + (size_t)n_rays * 8);
-    w.tmax = w.tmin + n_rays;
-    w.nsteps = reinterpret_cast<int32_t*>(w.tmax + n_rays);
-    w.masks = reinterpret_cast<unsigned long long*>(p + header_bytes(n_rays));
-    return w;
-}
 
 __global__ __launch_bounds__(256) void occ_march_count_kernel(const float* __restrict__ rays_o,
                                                               const float* __restrict__ rays_d, int64_t n_rays,
@@ -158,15 +138,11 @@ __global__ __launch_bounds__(256) void occ_march_write_kernel(int64_t n_rays, fl
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-bool valid_words(int32_t words) { return words >= 1 && words <= kMaxWords; }
-
 }  // namespace
 
 extern "C" size_t nerf_occ_march_workspace(int64_t n_rays, int32_t mask_words) {
-    if (n_rays < 0 || !valid_words(mask_words)) return 0;
-    return header_bytes(n_rays) + (size_t)n_rays * mask_words * sizeof(unsigned long long);
+    if (n_rays < 0 || !occ_valid_words(mask_words)) return 0;
+    return occ_workspace_bytes(n_rays, mask_words);
 }
 
 extern "C" int nerf_occ_march_count(const float* rays_o, const float* rays_d, int64_t n_rays, const float* aabb,
@@ -174,7 +150,7 @@ extern "C" int nerf_occ_march_count(const float* rays_o, const float* rays_d, in
                                     float far_plane, float step_size, int32_t stratified, uint64_t seed,
                                     uint64_t counter, int32_t mask_words, void* workspace, size_t workspace_bytes,
                                     int32_t* status, void* stream) {
-    NERF_REQUIRE(n_rays >= 0 && valid_words(mask_words) && aabb && resolution);
+    NERF_REQUIRE(n_rays >= 0 && occ_valid_words(mask_words) && aabb && resolution);
     NERF_REQUIRE(step_size > 0.0f && step_size < INFINITY);
     OccGrid g;
     int64_t cells = 1;
@@ -187,14 +163,15 @@ extern "C" int nerf_occ_march_count(const float* rays_o, const float* rays_d, in
     NERF_REQUIRE(cells <= (1ll << 31));
     if (n_rays == 0) return NERF_OK;
     NERF_REQUIRE(rays_o && rays_d && grid_bits && workspace && status);
-    NERF_REQUIRE(aligned(rays_o, 4) && aligned(rays_d, 4) && aligned(grid_bits, 4) && aligned(status, 4));
+    NERF_REQUIRE(occ_aligned(rays_o, 4) && occ_aligned(rays_d, 4) && occ_aligned(grid_bits, 4) &&
+                 occ_aligned(status, 4));
     NERF_REQUIRE((n_rays + 3) / 4 < (1ll << 31));
     if (workspace_bytes < nerf_occ_march_workspace(n_rays, mask_words)) return NERF_ERR_WORKSPACE;
-    NERF_REQUIRE(aligned(workspace, 256));
+    NERF_REQUIRE(occ_aligned(workspace, 256));
     dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
     hipLaunchKernelGGL(occ_march_count_kernel, grid, block, 0, as_stream(stream), rays_o, rays_d, n_rays, g, grid_bits,
                        near_plane, far_plane, step_size, stratified, seed, counter, mask_words,
-                       carve(workspace, n_rays), status);
+                       occ_carve(workspace, n_rays), status);
     NERF_CHECK_LAUNCH();
     return NERF_OK;
 }
@@ -202,18 +179,19 @@ extern "C" int nerf_occ_march_count(const float* rays_o, const float* rays_d, in
 extern "C" int nerf_occ_march_write(int64_t n_rays, float step_size, int32_t mask_words, const void* workspace,
                                     size_t workspace_bytes, const int64_t* offsets_incl, int64_t n_samples,
                                     int64_t* ray_indices, float* t_starts, float* t_ends, void* stream) {
-    NERF_REQUIRE(n_rays >= 0 && n_samples >= 0 && valid_words(mask_words));
+    NERF_REQUIRE(n_rays >= 0 && n_samples >= 0 && occ_valid_words(mask_words));
     NERF_REQUIRE(step_size > 0.0f && step_size < INFINITY);
     if (n_rays == 0 || n_samples == 0) return NERF_OK;
     NERF_REQUIRE(workspace && offsets_incl && ray_indices && t_starts && t_ends);
-    NERF_REQUIRE(aligned(offsets_incl, 8) && aligned(ray_indices, 8) && aligned(t_starts, 4) && aligned(t_ends, 4));
+    NERF_REQUIRE(occ_aligned(offsets_incl, 8) && occ_aligned(ray_indices, 8) && occ_aligned(t_starts, 4) &&
+                 occ_aligned(t_ends, 4));
     NERF_REQUIRE((n_rays + 3) / 4 < (1ll << 31));
     if (workspace_bytes < nerf_occ_march_workspace(n_rays, mask_words)) return NERF_ERR_WORKSPACE;
-    NERF_REQUIRE(aligned(workspace, 256));
+    NERF_REQUIRE(occ_aligned(workspace, 256));
     dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
     hipLaunchKernelGGL(occ_march_write_kernel, grid, block, 0, as_stream(stream), n_rays, step_size, mask_words,
-                       carve(const_cast<void*>(workspace), n_rays), offsets_incl, n_samples, ray_indices, t_starts,
-                       t_ends);
+                       occ_carve(const_cast<void*>(workspace), n_rays), offsets_incl, n_samples, ray_indices,
+                       t_starts, t_ends);
     NERF_CHECK_LAUNCH();
     return NERF_OK;
 }

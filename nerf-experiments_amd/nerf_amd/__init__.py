@@ -18,7 +18,7 @@ from .model_ingp2d import Gigapixel  # noqa: F401  (its INGPTable / INGPEncoding
 from .optim import FusedAdam  # noqa: F401
 from .pose import compute_pose_error, kabsch_algorithm, validation_transform_rays  # noqa: F401
 from .prop_sampler import PropNetEstimator, render_weight_from_density, rendering  # noqa: F401
-from .occ_grid import OccGridEstimator  # noqa: F401
+from .occ_grid import CascadedOccGridEstimator, OccGridEstimator  # noqa: F401
 from .occ_render import OccGridRenderer, distortion, packed_points  # noqa: F401
 
 __version__ = "0.1.0"

@@ -47,6 +47,7 @@ def NERF_FUSED_SPLIT_OUT(layer: int) -> int:
 NERF_KABSCH_MAX_POINTS = 4096
 NERF_PROP_MAX_EDGES = 512
 NERF_OCC_MAX_STEPS = 8192
+NERF_OCC_MAX_LEVELS = 8
 NERF_GAUSS_FWD = 0
 NERF_GAUSS_BWD = 1
 NERF_ACT_GABOR = 1
@@ -284,6 +285,9 @@ _SIGNATURES = {
     "nerf_occ_march_count": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_f), ctypes.POINTER(c_i32), c_vp, c_f, c_f,
                                      c_f, c_i32, c_u64, c_u64, c_i32, c_vp, c_sz, c_vp, c_vp]),
     "nerf_occ_march_write": (c_i32, [c_i64, c_f, c_i32, c_vp, c_sz, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "nerf_occ_cascade_count": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_f), c_i32, ctypes.POINTER(c_i32), c_vp, c_vp,
+                                       c_vp, c_f, c_f, c_f, c_f, c_i32, c_u64, c_u64, c_i32, c_vp, c_sz, c_vp, c_vp]),
+    "nerf_occ_cascade_write": (c_i32, [c_i64, c_f, c_f, c_i32, c_vp, c_sz, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "nerf_composite_packed_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_vp, c_vp]),
     "nerf_composite_packed_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,

@@ -1235,6 +1235,65 @@ def occ_march_write(n_rays: int, step_size: float, mask_words: int, workspace: t
     return ray_indices, t_starts, t_ends
 
 
+def occ_cascade_count(rays_o: torch.Tensor, rays_d: torch.Tensor, aabbs: Sequence[Sequence[float]],
+                      resolution: Sequence[int], grid_bits: torch.Tensor, near: float, far: float, step_size: float,
+                      cone_angle: float, stratified: bool, seed: int, mask_words: int, workspace: torch.Tensor,
+                      status: torch.Tensor, t_lo: torch.Tensor | None = None,
+                      t_hi: torch.Tensor | None = None) -> torch.Tensor:
+    """Pass 1 of the cascaded marching (nerf_occ_cascade_count): aabbs is the host's [levels][6] boxes,
+    grid_bits the packed [levels, rx, ry, rz] cells, t_lo / t_hi optional per-ray bounds.  Fills
+    `workspace` (occ_march_workspace_bytes) and returns the per-ray kept counts, an int64 [n_rays] view
+    of its first bytes."""
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d)):
+        _require_cuda_f32(name, t)
+        if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [n_rays, 3] tensor")
+    if rays_d.shape != rays_o.shape:
+        raise ValueError("rays_o and rays_d must share their shape")
+    n = rays_o.shape[0]
+    boxes = [[float(v) for v in box] for box in aabbs]
+    levels = len(boxes)
+    if not 1 <= levels <= _lib.NERF_OCC_MAX_LEVELS or any(len(box) != 6 for box in boxes):
+        raise ValueError(f"aabbs must hold 1..{_lib.NERF_OCC_MAX_LEVELS} boxes of six floats")
+    if grid_bits.dtype != torch.int32 or not grid_bits.is_contiguous() or grid_bits.device != rays_o.device:
+        raise ValueError("grid_bits must be a contiguous int32 tensor on the rays' device")
+    cells = int(resolution[0]) * int(resolution[1]) * int(resolution[2])
+    if grid_bits.numel() * 32 < levels * cells:
+        raise ValueError(f"grid_bits holds {grid_bits.numel() * 32} bits for {levels} x {cells} cells")
+    for name, t in (("t_min", t_lo), ("t_max", t_hi)):
+        if t is None:
+            continue
+        _require_cuda_f32(name, t)
+        if tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != rays_o.device:
+            raise ValueError(f"{name} must be a contiguous [n_rays] tensor on the rays' device")
+    box = (_lib.c_f * (6 * levels))(*[v for b in boxes for v in b])
+    res = (_lib.c_i32 * 3)(*[int(v) for v in resolution])
+    st = _lib.load().nerf_occ_cascade_count(_ptr(rays_o), _ptr(rays_d), n, box, levels, res, _ptr(grid_bits),
+                                            _ptr(t_lo), _ptr(t_hi), float(near), float(far), float(step_size),
+                                            float(cone_angle), int(stratified), seed, 0, mask_words, _ptr(workspace),
+                                            workspace.numel() * workspace.element_size(), _ptr(status),
+                                            _stream(rays_o.device))
+    _lib.check(st, "nerf_occ_cascade_count")
+    return workspace.view(torch.uint8)[:8 * n].view(torch.int64)
+
+
+def occ_cascade_write(n_rays: int, step_size: float, cone_angle: float, mask_words: int, workspace: torch.Tensor,
+                      offsets_incl: torch.Tensor, n_samples: int):
+    """Pass 2 (nerf_occ_cascade_write), with the step_size and cone_angle of pass 1: (ray_indices int64
+    [N], t_starts [N], t_ends [N]); offsets_incl is the inclusive prefix sum of pass 1's counts."""
+    if offsets_incl.dtype != torch.int64 or not offsets_incl.is_contiguous() or offsets_incl.numel() != n_rays:
+        raise ValueError("offsets_incl must be a contiguous int64 [n_rays] tensor")
+    dev = workspace.device
+    ray_indices = torch.empty(n_samples, device=dev, dtype=torch.int64)
+    t_starts = torch.empty(n_samples, device=dev, dtype=torch.float32)
+    t_ends = torch.empty(n_samples, device=dev, dtype=torch.float32)
+    st = _lib.load().nerf_occ_cascade_write(n_rays, float(step_size), float(cone_angle), mask_words, _ptr(workspace),
+                                            workspace.numel() * workspace.element_size(), _ptr(offsets_incl),
+                                            n_samples, _ptr(ray_indices), _ptr(t_starts), _ptr(t_ends), _stream(dev))
+    _lib.check(st, "nerf_occ_cascade_write")
+    return ray_indices, t_starts, t_ends
+
+
 # ----------------------------------------------------------------------------- packed compositing
 def _packed_inputs(sigma, rgb, t_starts, t_ends, seg):
     for name, t in (("sigma", sigma), ("t_starts", t_starts), ("t_ends", t_ends)):

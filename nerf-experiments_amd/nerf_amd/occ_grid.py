@@ -13,7 +13,11 @@ numerics are **parity unpinned**, like ``PropNetEstimator``'s.
     the marched samples are then filtered by opacity and transmittance
     (nerf_composite_packed_fwd); that compaction is a boolean index, a second synchronisation.
   * ``update_every_n_steps`` is nerfacc's schedule in plain torch ops (not a hot path).
-Out of scope: several levels, ``cone_angle``, per-ray ``t_min`` / ``t_max``, ``mark_invisible_cells``.
+  * ``CascadedOccGridEstimator`` is nerfacc's ``OccGridEstimator(levels=L)`` for unbounded scenes:
+    several levels, ``cone_angle`` and per-ray ``t_min`` / ``t_max`` through the cascaded marching
+    contract (nerf_occ_cascade_count / nerf_occ_cascade_write, csrc/occgrid_cascade.hip).  A class of
+    its own: ``OccGridEstimator`` keeps its one level, its kernels and its refusals.
+Out of scope: ``mark_invisible_cells``.
 """
 from __future__ import annotations
 
@@ -112,12 +116,17 @@ class OccGridEstimator(nn.Module):
             raise NotImplementedError("nerf_amd.occ_grid.OccGridEstimator.sampling supports cone_angle=0")
         if sigma_fn is not None and alpha_fn is not None:
             raise ValueError("give sigma_fn or alpha_fn, not both")
-        ray_indices, t_starts, t_ends = self._march(rays_o, rays_d, near_plane, far_plane, render_step_size,
-                                                    stratified)
+        marched = self._march(rays_o, rays_d, near_plane, far_plane, render_step_size, stratified)
+        return self._visible(*marched, rays_o.shape[0], sigma_fn, alpha_fn, early_stop_eps, alpha_thre)
+
+    @staticmethod
+    def _visible(ray_indices: th.Tensor, t_starts: th.Tensor, t_ends: th.Tensor, n_rays: int,
+                 sigma_fn: Optional[Callable], alpha_fn: Optional[Callable], early_stop_eps: float,
+                 alpha_thre: float):
+        """The visibility filter of ``sampling`` on marched samples."""
         if (sigma_fn is None and alpha_fn is None) or ray_indices.numel() == 0:
             return ray_indices, t_starts, t_ends
         from .prop_sampler import render_weight_from_density
-        n_rays = rays_o.shape[0]
         if sigma_fn is not None:
             sigmas = sigma_fn(t_starts, t_ends, ray_indices).reshape(-1).float()
             _, trans, alphas = render_weight_from_density(t_starts, t_ends, sigmas, ray_indices, n_rays)
@@ -161,4 +170,114 @@ class OccGridEstimator(nn.Module):
         self.binaries.copy_((self.occs > thre).view_as(self.binaries))
 
 
-__all__ = ["OccGridEstimator", "pack_grid_bits"]
+class CascadedOccGridEstimator(OccGridEstimator):
+    """nerfacc.OccGridEstimator(roi_aabb, resolution=128, levels=L) restated, for unbounded scenes:
+    Instant-NGP's cascaded grids.  Level l covers the region of interest enlarged 2^l times about its
+    centre, every level at the same resolution, so cells double in size away from it.  Buffers (in
+    ``state_dict``, nerfacc's layout): ``occs`` fp32 [levels * cells], ``binaries`` bool [levels, rx,
+    ry, rz]; ``aabbs`` fp32 [levels, 6] are the boxes the kernel is given.  ``sampling`` also takes
+    ``cone_angle >= 0`` (the step grows as t * cone_angle once that exceeds render_step_size) and per-ray
+    ``t_min`` / ``t_max``: nerf_occ_cascade_count / nerf_occ_cascade_write (csrc/occgrid_cascade.hip),
+    the cascaded marching contract of include/nerf_amd.h.  With levels=1, cone_angle=0 and no ray bounds
+    the samples are ``OccGridEstimator``'s bit for bit."""
+
+    def __init__(self, roi_aabb: Sequence[float], resolution: Union[int, Sequence[int]] = 128, levels: int = 1):
+        nn.Module.__init__(self)        # not the base's: it refuses levels != 1
+        levels = int(levels)
+        if not 1 <= levels <= K._lib.NERF_OCC_MAX_LEVELS:
+            raise ValueError(f"levels must lie in [1, {K._lib.NERF_OCC_MAX_LEVELS}]")
+        aabb = [float(v) for v in (roi_aabb.tolist() if isinstance(roi_aabb, th.Tensor) else roi_aabb)]
+        if len(aabb) != 6 or not all(lo < hi for lo, hi in zip(aabb[:3], aabb[3:])):
+            raise ValueError("roi_aabb must be [xmin, ymin, zmin, xmax, ymax, zmax] with min < max")
+        res = [int(resolution)] * 3 if isinstance(resolution, int) else [int(r) for r in resolution]
+        if len(res) != 3 or min(res) < 1:
+            raise ValueError("resolution must be a positive int or three of them")
+        self.aabb = tuple(aabb)
+        self.resolution = tuple(res)
+        self.levels = levels
+        self.cells = res[0] * res[1] * res[2]
+        # nerfacc's enlargement, every operation in fp32 (the contract: the kernel derives nothing)
+        lo, hi = th.tensor(aabb[:3], dtype=th.float32), th.tensor(aabb[3:], dtype=th.float32)
+        c, h = (lo + hi) * 0.5, (hi - lo) * 0.5
+        aabbs = th.stack([th.cat([c - h * 2.0 ** l, c + h * 2.0 ** l]) for l in range(levels)])
+        self._boxes = aabbs.tolist()    # the host copy the kernel call takes
+        self.register_buffer("aabbs", aabbs, persistent=False)
+        self.register_buffer("occs", th.zeros(levels * self.cells))
+        self.register_buffer("binaries", th.zeros([levels] + res, dtype=th.bool))
+        self._bits = None
+        self._bits_src = None
+        self._status = None
+
+    @th.no_grad()
+    def _march(self, rays_o: th.Tensor, rays_d: th.Tensor, near_plane: float, far_plane: float,
+               render_step_size: float, stratified: bool, cone_angle: float = 0.0,
+               t_min: Optional[th.Tensor] = None, t_max: Optional[th.Tensor] = None):
+        if self.binaries.device.type != "cuda":
+            raise RuntimeError("CascadedOccGridEstimator.sampling needs the estimator on a ROCm device; "
+                               "there is no CPU path")
+        rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
+        n_rays = rays_o.shape[0]
+        seed = _rng_seed() if stratified else 0
+        # a step is never shorter than render_step_size, so the lattice's capacity bounds every ray
+        words = K.occ_mask_words(near_plane, far_plane, render_step_size)
+        ws = th.empty(K.occ_march_workspace_bytes(n_rays, words), device=rays_o.device, dtype=th.uint8)
+        bound = lambda t: None if t is None else t.to(th.float32).contiguous()
+        counts = K.occ_cascade_count(rays_o, rays_d, self._boxes, self.resolution, self.grid_bits(), near_plane,
+                                     far_plane, render_step_size, cone_angle, stratified, seed, words, ws,
+                                     self.status(), bound(t_min), bound(t_max))
+        offsets = th.cumsum(counts, dim=0)
+        total = int(offsets[-1].item()) if n_rays else 0      # the one host synchronisation
+        return K.occ_cascade_write(n_rays, render_step_size, cone_angle, words, ws, offsets, total)
+
+    @th.no_grad()
+    def sampling(self, rays_o: th.Tensor, rays_d: th.Tensor, sigma_fn: Optional[Callable] = None,
+                 alpha_fn: Optional[Callable] = None, near_plane: float = 0.0, far_plane: float = 1e10,
+                 render_step_size: float = 1e-3, early_stop_eps: float = 1e-4, alpha_thre: float = 0.0,
+                 stratified: bool = False, cone_angle: float = 0.0, t_min: Optional[th.Tensor] = None,
+                 t_max: Optional[th.Tensor] = None):
+        """``OccGridEstimator.sampling`` through the cascade, plus ``cone_angle >= 0`` and per-ray
+        ``t_min`` / ``t_max`` (fp32 [n_rays], each optional; they narrow [near_plane, far_plane]).  The
+        same outputs, the same one host synchronisation, the same visibility filter."""
+        if not float(cone_angle) >= 0.0:
+            raise ValueError("cone_angle must be >= 0")
+        if sigma_fn is not None and alpha_fn is not None:
+            raise ValueError("give sigma_fn or alpha_fn, not both")
+        marched = self._march(rays_o, rays_d, near_plane, far_plane, render_step_size, stratified,
+                              float(cone_angle), t_min, t_max)
+        return self._visible(*marched, rays_o.shape[0], sigma_fn, alpha_fn, early_stop_eps, alpha_thre)
+
+    @th.no_grad()
+    def update_every_n_steps(self, step: int, occ_eval_fn: Callable, occ_thre: float = 1e-2, ema_decay: float = 0.95,
+                             warmup_steps: int = 256, n: int = 16) -> None:
+        """nerfacc's schedule per level: every n steps, ``occ_eval_fn`` at one jittered point of each
+        chosen cell, mapped into the cell's own level's box (all cells of all levels during warm-up,
+        afterwards per level a quarter drawn uniformly plus up to a quarter drawn from the level's
+        occupied cells); then one EMA and one threshold over all levels:
+        occs = max(occs * ema_decay, occ); binaries = occs > min(occ_thre, mean(occs))."""
+        if step % n != 0:
+            return
+        dev = self.occs.device
+        rx, ry, rz = self.resolution
+        res = th.tensor([rx, ry, rz], device=dev, dtype=th.float32)
+        boxes = self.aabbs
+        for l in range(self.levels):
+            if step < warmup_steps:
+                idx = th.arange(self.cells, device=dev)
+            else:
+                quarter = self.cells // 4
+                uniform = th.randint(self.cells, (quarter,), device=dev)
+                occupied = th.nonzero(self.binaries[l].reshape(-1))[:, 0]
+                if quarter < occupied.numel():
+                    occupied = occupied[th.randint(occupied.numel(), (quarter,), device=dev)]
+                idx = th.cat([uniform, occupied])
+            coords = th.stack([idx // (ry * rz), (idx // rz) % ry, idx % rz], dim=-1).float()
+            x = (coords + th.rand_like(coords)) / res
+            lo, hi = boxes[l, :3], boxes[l, 3:]
+            occ = occ_eval_fn(lo + x * (hi - lo)).reshape(-1).float()
+            idx = idx + l * self.cells
+            self.occs[idx] = th.maximum(self.occs[idx] * ema_decay, occ)
+        thre = th.clamp(self.occs.mean(), max=occ_thre)
+        self.binaries.copy_((self.occs > thre).view_as(self.binaries))
+
+
+__all__ = ["CascadedOccGridEstimator", "OccGridEstimator", "pack_grid_bits"]

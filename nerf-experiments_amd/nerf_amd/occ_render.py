@@ -141,7 +141,9 @@ def distortion(weights: th.Tensor, t_starts: th.Tensor, t_ends: th.Tensor, ray_i
 
 class OccGridRenderer(nn.Module):
     """Renders and trains any ``radiance(pos [N, 3], dir [N, 3]) -> (rgb [N, 3], density [N] or [N, 1])``
-    (the convention of the GARF / GaborF / SARF ``RadianceNetwork``) through an ``OccGridEstimator``.
+    (the convention of the GARF / GaborF / SARF ``RadianceNetwork``) through an ``OccGridEstimator``, or,
+    for unbounded scenes, a ``CascadedOccGridEstimator`` with ``cone_angle > 0`` (nerfacc's examples use
+    0.004 with four levels).
 
     ``forward(rays_o, rays_d, stratified=None)`` -> (rgb [R, 3], opacity [R, 1], depth [R, 1], extras):
     ``estimator.sampling`` (with the visibility filter, a no_grad density pass at the packed points,
@@ -156,7 +158,8 @@ class OccGridRenderer(nn.Module):
 
     def __init__(self, radiance: Callable, estimator: nn.Module, near_plane: float, far_plane: float,
                  render_step_size: float, alpha_thre: float = 0.0, early_stop_eps: float = 1e-4,
-                 render_bkgd: Optional[th.Tensor] = None, density_fn: Optional[Callable] = None):
+                 render_bkgd: Optional[th.Tensor] = None, density_fn: Optional[Callable] = None,
+                 cone_angle: float = 0.0):
         super().__init__()
         self.radiance = radiance
         self.estimator = estimator
@@ -166,6 +169,7 @@ class OccGridRenderer(nn.Module):
         self.register_buffer("render_bkgd", None if render_bkgd is None
                              else th.as_tensor(render_bkgd, dtype=th.float32).clone())
         self.density_fn = density_fn
+        self.cone_angle = float(cone_angle)
         self._n_rays = None
 
     def _density(self, pos: th.Tensor, dirs: Optional[th.Tensor] = None) -> th.Tensor:
@@ -188,10 +192,12 @@ class OccGridRenderer(nn.Module):
             def sigma_fn(ts, te, idx):                   # called under sampling's no_grad
                 pos, dirs = packed_points(o_s, d_s, idx, ts, te, R, want_dirs=self.density_fn is None)
                 return self._density(pos, dirs)
+        # cone_angle is passed only when set: a one-level estimator is called exactly as before
+        cone = {"cone_angle": self.cone_angle} if self.cone_angle != 0.0 else {}
         ray_indices, t_starts, t_ends = self.estimator.sampling(
             o_s, d_s, sigma_fn=sigma_fn, near_plane=self.near_plane, far_plane=self.far_plane,
             render_step_size=self.render_step_size, early_stop_eps=self.early_stop_eps, alpha_thre=self.alpha_thre,
-            stratified=bool(stratified))
+            stratified=bool(stratified), **cone)
         where = {"ray_indices": ray_indices, "t_starts": t_starts, "t_ends": t_ends}
         if ray_indices.numel() == 0:                    # a shape: known on the host since sampling
             f = dict(device=rays_o.device, dtype=th.float32)
