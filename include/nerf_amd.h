@@ -1068,6 +1068,70 @@ int nerf_distortion_fwd(const float* weights, const float* t_starts, const float
 int nerf_distortion_bwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* seg,
                         int64_t n_rays, int64_t n_samples, const float* g_loss, float* grad_weights, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-sample pieces of the Instant-NGP radiance field (nerf_amd/model_ngp.py): the real
+ * spherical-harmonics direction encoding of tiny-cuda-nn and the position map of nerfacc's
+ * NGPRadianceField, both restated from their published behaviour (parity unpinned).  One thread per
+ * sample, no atomics: bitwise reproducible.  No store at or past row n, and none to a column not
+ * named below.
+ *
+ * The SH contract, every operation rounded to fp32 separately (no contraction), the constants
+ * rounded to fp32 once, for row i with (x, y, z) = dirs[i][0..2] (row stride dirs_stride >= 3) used
+ * as given (the caller normalises; tiny-cuda-nn's (d + 1) / 2 and 2u - 1 round trip is not made):
+ *   1. degree >= 1:  out[i][0] = 0.28209479177387814
+ *   2. degree >= 2:  out[i][1] = (-0.48860251190291987) * y;  [2] = 0.48860251190291987 * z;
+ *                    [3] = (-0.48860251190291987) * x
+ *   3. degree >= 3:  xx = x*x, yy = y*y, zz = z*z, xy = x*y, yz = y*z, xz = x*z;
+ *                    [4] = 1.0925484305920792 * xy;        [5] = (-1.0925484305920792) * yz;
+ *                    [6] = 0.94617469575755997 * zz - 0.31539156525251999;
+ *                    [7] = (-1.0925484305920792) * xz;     [8] = 0.54627421529603959 * (xx - yy)
+ *   4. degree == 4:  w = 1 - 5 * zz;
+ *                    [9]  = (0.59004358992664352 * y) * ((-3) * xx + yy);
+ *                    [10] = (2.8906114426405538 * xy) * z;
+ *                    [11] = (0.45704579946446572 * y) * w;
+ *                    [12] = (0.3731763325901154 * z) * (5 * zz - 3);
+ *                    [13] = (0.45704579946446572 * x) * w;
+ *                    [14] = (1.4453057213202769 * z) * (xx - yy);
+ *                    [15] = (0.59004358992664352 * x) * ((-xx) + 3 * yy)
+ * (tiny-cuda-nn's order and sign; orthonormal over the sphere).  Row stride out_ld >= degree^2;
+ * columns degree^2.. of a row are not touched.
+ * nerf_sh_encode_bwd: grad_dirs[i][a] = sum_c grad_out[i][c] dY_c/dd_a from the polynomials' analytic
+ * derivatives at dirs[i], c ascending, fp32 accumulation, overwritten (row strides g_ld >= degree^2,
+ * gd_stride >= 3; columns 3.. not touched).  Per sample: the sum over a ray's samples is
+ * nerf_packed_points_bwd's (its g_dirs input).
+ *
+ * The unit-cube contract, every operation rounded to fp32 separately, for row i of x (row stride
+ * x_stride >= 3) and the box aabb = (lo_0, lo_1, lo_2, hi_0, hi_1, hi_2), six floats read on the
+ * host and passed to the kernel by value:
+ *   1. e_a = hi_a - lo_a, once per axis;
+ *   2. v_a = (x_a - lo_a) / e_a.   mode 0 (bounded): u_a = v_a; go to 7.
+ *   3. c_a = v_a * 2 - 1;
+ *   4. m = max_a |c_a| (fmaxf: a NaN operand is ignored);
+ *   5. if m > 1:  s = 2 - 1 / m;  q_a = c_a / m;  c_a = s * q_a;
+ *   6. u_a = c_a / 4 + 0.5          (mode 1: nerfacc's contract_to_unisphere with the inf-norm)
+ *   7. u[i][a] = u_a (row stride u_stride >= 3, columns 3.. not touched);  inside[i] = 1 when
+ *      0 < u_a < 1 for all three a, else 0 (fp32 [n]; NULL: skipped).  A NaN coordinate gives a NaN
+ *      u_a and inside = 0.
+ * nerf_unit_cube_bwd (recomputes steps 1-4 from x):
+ *   mode 0: grad_x_a = grad_u_a / e_a;      mode 1, not m > 1: grad_x_a = grad_u_a / (2 e_a);
+ *   mode 1, m > 1, k the lowest index with |c_k| = m, y = (2m - 1) c / m^2:
+ *     dy_j/dc_i = (s / m) delta_ij + c_j sgn(c_k) delta_ik (2 - 2m) / m^3   (so dy_k/dc_k = 1 / m^2),
+ *     grad_x_i = (sum_j grad_u_j dy_j/dc_i) / (2 e_i), the sum over j ascending.
+ * inside carries no gradient.  Row strides gu_stride, gx_stride >= 3; columns 3.. not touched.
+ *
+ * All four: no output buffer may overlap an input or another output (the kernels do not work in place:
+ * u on x or grad_x on grad_u is not supported and not detected).  n == 0: NERF_OK without a launch; null or misaligned pointers, a row stride below the
+ * row width, degree outside 1..4 or mode outside {0, 1}: NERF_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------- */
+int nerf_sh_encode_fwd(const float* dirs, int64_t dirs_stride, int64_t n, int degree, float* out, int64_t out_ld,
+                       void* stream);
+int nerf_sh_encode_bwd(const float* dirs, int64_t dirs_stride, int64_t n, int degree, const float* grad_out,
+                       int64_t g_ld, float* grad_dirs, int64_t gd_stride, void* stream);
+int nerf_unit_cube_fwd(const float* x, int64_t x_stride, int64_t n, const float* aabb, int mode, float* u,
+                       int64_t u_stride, float* inside, void* stream);
+int nerf_unit_cube_bwd(const float* x, int64_t x_stride, int64_t n, const float* aabb, int mode,
+                       const float* grad_u, int64_t gu_stride, float* grad_x, int64_t gx_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,5 +20,7 @@ from .pose import compute_pose_error, kabsch_algorithm, validation_transform_ray
 from .prop_sampler import PropNetEstimator, render_weight_from_density, rendering  # noqa: F401
 from .occ_grid import CascadedOccGridEstimator, OccGridEstimator  # noqa: F401
 from .occ_render import OccGridRenderer, distortion, packed_points  # noqa: F401
+from .model_ngp import (NGPRadianceField, SHEncoding, contract_to_unisphere, normalize_to_aabb,  # noqa: F401
+                        trunc_exp)
 
 __version__ = "0.1.0"

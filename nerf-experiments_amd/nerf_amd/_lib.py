@@ -296,6 +296,10 @@ _SIGNATURES = {
     "nerf_packed_points_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "nerf_distortion_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "nerf_distortion_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "nerf_sh_encode_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "nerf_sh_encode_bwd": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "nerf_unit_cube_fwd": (c_i32, [c_vp, c_i64, c_i64, ctypes.POINTER(c_f), c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "nerf_unit_cube_bwd": (c_i32, [c_vp, c_i64, c_i64, ctypes.POINTER(c_f), c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

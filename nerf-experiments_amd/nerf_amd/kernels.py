@@ -1466,3 +1466,100 @@ def distortion_bwd(weights: torch.Tensor, t_starts: torch.Tensor, t_ends: torch.
         end.record()
     _lib.check(st, "nerf_distortion_bwd")
     return grad
+
+
+# ----------------------------------------------------------------------------- NGP field: SH encoding, position map
+def _row_stride(t: torch.Tensor) -> int:
+    """The row stride handed to a kernel: a tensor of at most one row may carry any stride(0) (a
+    transposed [3, 1] is a contiguous [1, 3]); no second row is ever addressed, so its width serves."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _rows3(name: str, t: torch.Tensor, n: int | None = None) -> int:
+    _require_cuda_f32(name, t)
+    if t.dim() != 2 or t.shape[1] < 3 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) \
+            or (n is not None and t.shape[0] != n):
+        raise ValueError(f"{name} must be a row-major [n, >= 3] tensor (got {tuple(t.shape)})")
+    return t.shape[0]
+
+
+def _check_degree(degree: int) -> int:
+    if not 1 <= int(degree) <= 4:
+        raise ValueError(f"degree must be in 1..4 (got {degree})")
+    return int(degree)
+
+
+def _sh_rows(name: str, t: torch.Tensor, n: int, degree: int) -> None:
+    _require_cuda_f32(name, t)
+    if t.dim() != 2 or t.shape[0] != n or t.shape[1] < degree * degree or t.stride(1) != 1 \
+            or (n > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name} must be a row-major [{n}, >= {degree * degree}] tensor (got {tuple(t.shape)})")
+
+
+def sh_encode_fwd(dirs: torch.Tensor, degree: int, out: torch.Tensor) -> None:
+    """nerf_sh_encode_fwd: columns 0 .. degree^2 - 1 of out's rows; the others are not touched."""
+    degree = _check_degree(degree)
+    n = _rows3("dirs", dirs)
+    _sh_rows("out", out, n, degree)
+    end = TIMER.bracket("sh_encode_fwd", nbytes=n * (12 + 4 * degree * degree), fn="sh_encode_fwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_sh_encode_fwd(_ptr(dirs), _row_stride(dirs), n, degree, _ptr(out), _row_stride(out),
+                                        _stream(dirs.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_sh_encode_fwd")
+
+
+def sh_encode_bwd(dirs: torch.Tensor, degree: int, grad_out: torch.Tensor) -> torch.Tensor:
+    """nerf_sh_encode_bwd: grad_dirs [n, 3], per sample."""
+    degree = _check_degree(degree)
+    n = _rows3("dirs", dirs)
+    _sh_rows("grad_out", grad_out, n, degree)
+    gd = torch.empty(n, 3, device=dirs.device, dtype=torch.float32)
+    end = TIMER.bracket("sh_encode_bwd", nbytes=n * (24 + 4 * degree * degree), fn="sh_encode_bwd_kernel") \
+        if TIMER is not None else None
+    st = _lib.load().nerf_sh_encode_bwd(_ptr(dirs), _row_stride(dirs), n, degree, _ptr(grad_out), _row_stride(grad_out),
+                                        _ptr(gd), 3, _stream(dirs.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_sh_encode_bwd")
+    return gd
+
+
+def _box(aabb: Sequence[float]):
+    vals = [float(v) for v in aabb]
+    if len(vals) != 6:
+        raise ValueError("aabb must hold six floats (lo_0, lo_1, lo_2, hi_0, hi_1, hi_2)")
+    return (_lib.c_f * 6)(*vals)
+
+
+def unit_cube_fwd(x: torch.Tensor, aabb: Sequence[float], mode: int):
+    """nerf_unit_cube_fwd: (u [n, 3], inside [n]); mode 0 normalises to the box, mode 1 contracts."""
+    if mode not in (0, 1):
+        raise ValueError(f"mode must be 0 (bounded) or 1 (contracted) (got {mode})")
+    n = _rows3("x", x)
+    u = torch.empty(n, 3, device=x.device, dtype=torch.float32)
+    inside = torch.empty(n, device=x.device, dtype=torch.float32)
+    end = TIMER.bracket("unit_cube_fwd", nbytes=n * 28, fn="unit_cube_fwd_kernel") if TIMER is not None else None
+    st = _lib.load().nerf_unit_cube_fwd(_ptr(x), _row_stride(x), n, _box(aabb), mode, _ptr(u), 3, _ptr(inside),
+                                        _stream(x.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_unit_cube_fwd")
+    return u, inside
+
+
+def unit_cube_bwd(x: torch.Tensor, aabb: Sequence[float], mode: int, grad_u: torch.Tensor) -> torch.Tensor:
+    """nerf_unit_cube_bwd: grad_x [n, 3]."""
+    if mode not in (0, 1):
+        raise ValueError(f"mode must be 0 (bounded) or 1 (contracted) (got {mode})")
+    n = _rows3("x", x)
+    _rows3("grad_u", grad_u, n)
+    gx = torch.empty(n, 3, device=x.device, dtype=torch.float32)
+    end = TIMER.bracket("unit_cube_bwd", nbytes=n * 36, fn="unit_cube_bwd_kernel") if TIMER is not None else None
+    st = _lib.load().nerf_unit_cube_bwd(_ptr(x), _row_stride(x), n, _box(aabb), mode, _ptr(grad_u), _row_stride(grad_u),
+                                        _ptr(gx), 3, _stream(x.device))
+    if end is not None:
+        end.record()
+    _lib.check(st, "nerf_unit_cube_bwd")
+    return gx
