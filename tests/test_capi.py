@@ -190,6 +190,10 @@ def test_argument_validation_returns_status_without_launch():
     assert lib.nerf_prop_sample(16, 65, 16, 65, 4, 64, 8, 0, 0, 0, 1, 0.0, 7.0, 16, 16, 16, None) == -1
     assert lib.nerf_prop_sample(16, 65, 16, 65, 0, 64, 8, 0, 0, 0, 1, 2.0, 7.0, 16, 16, 16, None) == 0
     assert lib.nerf_prop_loss(16, 16, 193, 16, 16, 65, 4, 192, 64, 1e-7, None, 0.0, None, 0, None) == -1
+    # one edge over NERF_PROP_MAX_EDGES = 512 (the kernels' static LDS rows): K + 1 = 513, n + 1 = 513
+    assert lib.nerf_prop_sample(16, 513, 16, 513, 4, 512, 8, 0, 0, 0, 1, 2.0, 7.0, 16, 16, 16, None) == -1
+    assert lib.nerf_prop_loss(16, 16, 513, 16, 16, 65, 4, 512, 64, 1e-7, 16, 0.0, 16, 64, None) == -1
+    assert lib.nerf_prop_loss(16, 16, 65, 16, 16, 513, 4, 64, 512, 1e-7, 16, 0.0, 16, 512, None) == -1
     assert lib.nerf_prop_cdf(16, 63, 4, 64, 16, 65, None) == -1
     assert lib.nerf_prop_cdf(None, 64, 0, 64, None, 65, None) == 0
     # ray-mode encoding backward: missing rays / outputs
