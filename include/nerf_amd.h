@@ -724,6 +724,13 @@ typedef struct nerf_hashgrid_params {
 /* Rows of level `level`'s table, or of the whole packed table when level < 0 (-1 on bad params). */
 int64_t nerf_hashgrid_table_rows(const nerf_hashgrid_params* params, int32_t level);
 
+/* Only the levels * features columns of the n_samples rows of out (row stride out_ld) are stored.
+ * Status codes of the three entry points, returned before any launch: invalid params, out_ld / g_ld <
+ * levels * features, a missing ray input, null data pointers with n_samples > 0:
+ * NERF_ERR_INVALID_ARG; a short workspace: NERF_ERR_WORKSPACE; a misaligned one:
+ * NERF_ERR_INVALID_ARG.  n_samples == 0 succeeds without a kernel and dereferences no data pointer
+ * (all may be NULL); a non-accumulating nerf_hashgrid_bwd then clears grad_table with a memset when
+ * it is given. */
 int nerf_hashgrid_fwd(const nerf_hashgrid_params* params, const float* x, const float* ray_o,
                       const float* ray_d, const float* t_start, const float* t_end, int64_t n_samples,
                       int32_t samples_per_ray, const float* table, float* out, int64_t out_ld, void* stream);
@@ -732,8 +739,14 @@ int nerf_hashgrid_fwd(const nerf_hashgrid_params* params, const float* x, const 
  * contribution w * g rounded to a 64-bit fixed-point grid 2^-s chosen from the batch's max |g| (no
  * entry can overflow) and added with integer atomics, so the result does not depend on their order
  * (deterministic); then grad_table = acc * 2^-s (+= if accumulate).  A non-finite grad_out gives
- * NaN.  workspace: nerf_hashgrid_workspace(params) bytes, 256-byte aligned; zeroed by the call
- * itself (no state is carried between calls). */
+ * NaN.  The rule is reproducible bit for bit on a CPU: gmax = max |grad_out| over the
+ * [n_samples][levels * features] block (columns beyond it are never read); non-finite gmax: every
+ * entry NaN; gmax == 0: s = 60; else with 8 * n_samples * gmax < 2^e (frexp of the fp64 product
+ * (8.0 * n_samples) * gmax) s = min(62 - e, 120).  Every corner adds
+ * llrint((double)w * ((double)g * 2^s)) to a 64-bit integer accumulator of its (row, f); then
+ * grad_table = (float)((double)acc * 2^-s), or += in fp32 when accumulate.  Every kernel path and
+ * either workspace size gives these bits.  workspace: nerf_hashgrid_workspace(params) bytes,
+ * 256-byte aligned; zeroed by the call itself (no state is carried between calls). */
 size_t nerf_hashgrid_workspace(const nerf_hashgrid_params* params);
 /* (ABI 8) workspace for n_samples: nerf_hashgrid_workspace(params) rounded up to 256 bytes, room for
  * grad_out restaged level-major (n_samples * levels * features fp32) and per-sample position

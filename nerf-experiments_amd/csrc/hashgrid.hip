@@ -1107,11 +1107,13 @@ extern "C" int nerf_hashgrid_fwd(const nerf_hashgrid_params* params, const float
                                  const float* ray_d, const float* t_start, const float* t_end, int64_t n_samples,
                                  int32_t samples_per_ray, const float* table, float* out, int64_t out_ld,
                                  void* stream) {
-    NERF_REQUIRE(valid_params(params) && table != nullptr && out != nullptr && n_samples >= 0);
+    NERF_REQUIRE(valid_params(params) && n_samples >= 0);
     NERF_REQUIRE(out_ld >= (int64_t)params->levels * params->features);
+    // an empty batch touches nothing: null data pointers are rejected only with n_samples > 0
+    if (n_samples == 0) return NERF_OK;
+    NERF_REQUIRE(table != nullptr && out != nullptr);
     NERF_REQUIRE(x != nullptr || (ray_o && ray_d && t_start && samples_per_ray >= 1 &&
                                   (params->query == 0 || t_end)));
-    if (n_samples == 0) return NERF_OK;
     const HashArgs a = make_args(params, x, ray_o, ray_d, t_start, t_end, n_samples, samples_per_ray);
     // NERF_HG_FWD: 1 (default) the level grid; 2 64-sample tiles, one wave per level, whole output
     // rows; 0 one thread per (sample, level) — bitwise the same features (1.31 M samples x 16 levels:
@@ -1142,8 +1144,11 @@ extern "C" int nerf_hashgrid_bwd_pos(const nerf_hashgrid_params* params, const f
                                      int32_t samples_per_ray, const float* table, const float* grad_out, int64_t g_ld,
                                      float* grad_x, float* grad_o, float* grad_d, int32_t accumulate, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    NERF_REQUIRE(valid_params(params) && table != nullptr && grad_out != nullptr && n_samples >= 0);
+    NERF_REQUIRE(valid_params(params) && n_samples >= 0);
     NERF_REQUIRE(g_ld >= (int64_t)params->levels * params->features);
+    // an empty batch adds nothing to any output: null data pointers are rejected only with n_samples > 0
+    if (n_samples == 0) return NERF_OK;
+    NERF_REQUIRE(table != nullptr && grad_out != nullptr);
     if (x != nullptr) {
         NERF_REQUIRE(grad_x != nullptr && grad_o == nullptr && grad_d == nullptr);
     } else {
@@ -1153,7 +1158,6 @@ extern "C" int nerf_hashgrid_bwd_pos(const nerf_hashgrid_params* params, const f
         if (workspace == nullptr || workspace_bytes < (size_t)n_samples * 3 * sizeof(float)) return NERF_ERR_WORKSPACE;
         NERF_REQUIRE(aligned16(workspace));
     }
-    if (n_samples == 0) return NERF_OK;
     NERF_REQUIRE((n_samples + 255) / 256 < (1ll << 31));
     const HashArgs a = make_args(params, x, ray_o, ray_d, t_start, t_end, n_samples, samples_per_ray);
     hipStream_t st = as_stream(stream);
@@ -1241,16 +1245,27 @@ extern "C" int nerf_hashgrid_bwd(const nerf_hashgrid_params* params, const float
                                  const float* ray_d, const float* t_start, const float* t_end, int64_t n_samples,
                                  int32_t samples_per_ray, const float* grad_out, int64_t g_ld, float* grad_table,
                                  int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-    NERF_REQUIRE(valid_params(params) && grad_out != nullptr && grad_table != nullptr && workspace != nullptr);
-    NERF_REQUIRE(n_samples >= 0 && g_ld >= (int64_t)params->levels * params->features);
-    NERF_REQUIRE(x != nullptr || (ray_o && ray_d && t_start && samples_per_ray >= 1 &&
-                                  (params->query == 0 || t_end)));
-    if (workspace_bytes < nerf_hashgrid_workspace(params)) return NERF_ERR_WORKSPACE;
-    NERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0);
-    unsigned* gmax = static_cast<unsigned*>(workspace);
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + 256);
+    NERF_REQUIRE(valid_params(params) && n_samples >= 0);
+    NERF_REQUIRE(g_ld >= (int64_t)params->levels * params->features);
+    // null data pointers are rejected only with n_samples > 0
+    NERF_REQUIRE(n_samples == 0 || (grad_out != nullptr && grad_table != nullptr && workspace != nullptr));
+    NERF_REQUIRE(n_samples == 0 || x != nullptr || (ray_o && ray_d && t_start && samples_per_ray >= 1 &&
+                                                    (params->query == 0 || t_end)));
+    if (workspace != nullptr) {
+        if (workspace_bytes < nerf_hashgrid_workspace(params)) return NERF_ERR_WORKSPACE;
+        NERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0);
+    }
     const int64_t count = total_rows(params) * params->features;
     hipStream_t s = as_stream(stream);
+    if (n_samples == 0) {
+        // nothing to add: a plain gradient is zero, an accumulated one unchanged (no kernel)
+        if (!accumulate && grad_table != nullptr &&
+            hipMemsetAsync(grad_table, 0, (size_t)count * sizeof(float), s) != hipSuccess)
+            return NERF_ERR_LAUNCH;
+        return NERF_OK;
+    }
+    unsigned* gmax = static_cast<unsigned*>(workspace);
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + 256);
     // header and accumulators zeroed by every call (no state carried between calls)
     if (hipMemsetAsync(workspace, 0, 256 + (size_t)count * sizeof(unsigned long long), s) != hipSuccess)
         return NERF_ERR_LAUNCH;

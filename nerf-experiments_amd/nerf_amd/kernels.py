@@ -837,6 +837,16 @@ def _hashgrid_table_check(name: str, params, table: torch.Tensor) -> None:
                          f"(got {tuple(table.shape)})")
 
 
+def _hashgrid_rows(name: str, t: torch.Tensor, n_samples: int, cols: int) -> int:
+    """Validate a row-major [>= n_samples, >= cols] tensor and return its row stride.  An empty batch's
+    rows are never read or written, so its strides (an expanded empty gradient has stride 0) are not
+    looked at and the stride handed to the library is cols."""
+    _require_cuda_f32(name, t)
+    if t.dim() != 2 or t.shape[0] < n_samples or t.shape[1] < cols or (n_samples > 0 and t.stride(1) != 1):
+        raise ValueError(f"{name} must be a row-major [>= {n_samples}, >= {cols}] tensor (got {tuple(t.shape)})")
+    return t.stride(0) if n_samples > 0 else cols
+
+
 # the kernels the library runs (NERF_HG_FWD: 1 (default) the level grid, 2 64-sample tiles with whole
 # output rows, 0 one thread per (sample, level); NERF_HG_BWD: 0 (default) the per-item grid on the
 # rows, 1 the per-item grid over grad_out restaged level-major, 2 the persistent part walk over it —
@@ -855,9 +865,7 @@ HASHGRID_BWD_FN = ("hashgrid_bwd_walk_kernel" if os.environ.get("NERF_HG_BWD", "
 def hashgrid_fwd(params, table: torch.Tensor, out: torch.Tensor, *, x=None, ray_o=None, ray_d=None, t_start=None,
                  t_end=None, n_samples: int, samples_per_ray: int = 1) -> None:
     _hashgrid_table_check("table", params, table)
-    _require_cuda_f32("out", out)
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_samples or out.shape[1] < params.levels * params.features:
-        raise ValueError("out must be a row-major [n, >= levels * features] tensor")
+    out_ld = _hashgrid_rows("out", out, n_samples, params.levels * params.features)
     _hashgrid_inputs(params, n_samples, x, ray_o, ray_d, t_start, t_end, samples_per_ray)
     # algorithmic bytes: 8 corners x F fp32 gathered + F fp32 written per (sample, level)
     end = TIMER.bracket("hashgrid_fwd", 0.0, 8.0 * n_samples * params.levels * params.features * 4
@@ -865,7 +873,7 @@ def hashgrid_fwd(params, table: torch.Tensor, out: torch.Tensor, *, x=None, ray_
         if TIMER is not None else None
     st = _lib.load().nerf_hashgrid_fwd(ctypes.byref(params), _ptr(x), _ptr(ray_o), _ptr(ray_d), _ptr(t_start),
                                        _ptr(t_end), n_samples, samples_per_ray, table.data_ptr(), out.data_ptr(),
-                                       out.stride(0), _stream(table.device))
+                                       out_ld, _stream(table.device))
     if end is not None:
         end.record()
     _lib.check(st, "nerf_hashgrid_fwd")
@@ -888,19 +896,15 @@ def hashgrid_bwd_pos(params, table: torch.Tensor, grad_out: torch.Tensor, *, x=N
                      want_d: bool = True):
     """Position gradient through the hash grid (nerf_hashgrid_bwd_pos): grad_x [n, 3] for explicit
     positions, else (grad_o, grad_d) [n_rays, 3] (None where not wanted) for ray-mode samples."""
-    _require_cuda_f32("grad_out", grad_out)
+    g_ld = _hashgrid_rows("grad_out", grad_out, n_samples, params.levels * params.features)
     _hashgrid_table_check("table", params, table)
-    if grad_out.dim() != 2 or grad_out.stride(1) != 1 or grad_out.shape[0] < n_samples \
-            or grad_out.shape[1] < params.levels * params.features:
-        raise ValueError(f"grad_out must be a row-major [>= {n_samples}, >= {params.levels * params.features}] "
-                         f"tensor (got {tuple(grad_out.shape)})")
     _hashgrid_inputs(params, n_samples, x, ray_o, ray_d, t_start, t_end, samples_per_ray)
     dev = grad_out.device
     lib = _lib.load()
     if x is not None:
         gx = torch.empty(n_samples, 3, device=dev, dtype=torch.float32)
         st = lib.nerf_hashgrid_bwd_pos(ctypes.byref(params), _ptr(x), None, None, None, None, n_samples, 1,
-                                       table.data_ptr(), grad_out.data_ptr(), grad_out.stride(0), gx.data_ptr(),
+                                       table.data_ptr(), grad_out.data_ptr(), g_ld, gx.data_ptr(),
                                        None, None, 0, None, 0, _stream(dev))
         _lib.check(st, "nerf_hashgrid_bwd_pos")
         return gx
@@ -910,7 +914,7 @@ def hashgrid_bwd_pos(params, table: torch.Tensor, grad_out: torch.Tensor, *, x=N
     ws = torch.empty(max(1, n_samples * 3), device=dev, dtype=torch.float32)
     st = lib.nerf_hashgrid_bwd_pos(ctypes.byref(params), None, _ptr(ray_o), _ptr(ray_d), _ptr(t_start), _ptr(t_end),
                                    n_samples, samples_per_ray, table.data_ptr(), grad_out.data_ptr(),
-                                   grad_out.stride(0), None, _ptr(go), _ptr(gd), 0, ws.data_ptr(),
+                                   g_ld, None, _ptr(go), _ptr(gd), 0, ws.data_ptr(),
                                    ws.numel() * 4, _stream(dev))
     _lib.check(st, "nerf_hashgrid_bwd_pos")
     return go, gd
@@ -919,12 +923,8 @@ def hashgrid_bwd_pos(params, table: torch.Tensor, grad_out: torch.Tensor, *, x=N
 def hashgrid_bwd(params, grad_out: torch.Tensor, grad_table: torch.Tensor, workspace: torch.Tensor, *, x=None,
                  ray_o=None, ray_d=None, t_start=None, t_end=None, n_samples: int, samples_per_ray: int = 1,
                  accumulate: bool = False) -> None:
-    _require_cuda_f32("grad_out", grad_out)
+    g_ld = _hashgrid_rows("grad_out", grad_out, n_samples, params.levels * params.features)
     _hashgrid_table_check("grad_table", params, grad_table)
-    if grad_out.dim() != 2 or grad_out.stride(1) != 1 or grad_out.shape[0] < n_samples \
-            or grad_out.shape[1] < params.levels * params.features:
-        raise ValueError(f"grad_out must be a row-major [>= {n_samples}, >= {params.levels * params.features}] "
-                         f"tensor (got {tuple(grad_out.shape)})")
     _hashgrid_inputs(params, n_samples, x, ray_o, ray_d, t_start, t_end, samples_per_ray)
     need = hashgrid_workspace_bytes(params)
     if workspace.device != grad_out.device or not workspace.is_contiguous() \
@@ -936,7 +936,7 @@ def hashgrid_bwd(params, grad_out: torch.Tensor, grad_table: torch.Tensor, works
         if TIMER is not None else None
     st = _lib.load().nerf_hashgrid_bwd(ctypes.byref(params), _ptr(x), _ptr(ray_o), _ptr(ray_d), _ptr(t_start),
                                        _ptr(t_end), n_samples, samples_per_ray, grad_out.data_ptr(),
-                                       grad_out.stride(0), grad_table.data_ptr(), int(accumulate),
+                                       g_ld, grad_table.data_ptr(), int(accumulate),
                                        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                                        _stream(grad_out.device))
     if end is not None:

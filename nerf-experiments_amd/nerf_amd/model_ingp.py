@@ -120,13 +120,16 @@ class _HashGridFn(th.autograd.Function):
         # the packed table is read back only by the position gradient: saving it otherwise would make any
         # in-place table update between forward and backward trip autograd's version check
         keep = packed if any(ctx.needs_input_grad[4:7]) else None
-        ctx.save_for_backward(*(t if t is not None else th.empty(0) for t in (x, ray_o, ray_d, t_start, t_end, keep)))
+        saved = (x, ray_o, ray_d, t_start, t_end, keep)
+        # which inputs were given: an empty batch's tensors are empty too, so numel() cannot tell
+        ctx.given = tuple(t is not None for t in saved)
+        ctx.save_for_backward(*(t if t is not None else th.empty(0) for t in saved))
         return out
 
     @staticmethod
     def backward(ctx, g):
         spr, n, shape = ctx.meta
-        x, o, d, t0, t1, packed = (t if t.numel() else None for t in ctx.saved_tensors)
+        x, o, d, t0, t1, packed = (t if given else None for t, given in zip(ctx.saved_tensors, ctx.given))
         grads = [None] * len(ctx.rows)
         gx = go = gd = None
         if g is not None and any(ctx.needs_input_grad[12:]):
